@@ -10,7 +10,13 @@ data: synthetic U[0,1] clips resident in HBM.
 
   python bench.py --gpus N --steps K --warmup W      (N>1 under torch.distributed.run)
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps
+and prints the headline figures (value, ms_per_step); the extra objects are
+null.  --dump-outputs DIR also writes what the last timed step computed (its
+loss and the updated unet parameters) as DIR/<name>.npy; that step then
+starts from the restored initial state, so that its inputs are the same in
+every run (dump_outputs).  --full adds the
+extra objects, each a measurement of its own after the timed steps:
   roofline      dominant kernel (HIP events on its launch stream, live)
   conv_shapes   the same per (kernel, GEMM shape) — the actionable rows
   attention     mid MQA QK^T/PV fwd+bwd vs the bf16 MFMA peak (north-star target)
@@ -57,6 +63,11 @@ def parse():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--size", type=int, default=64)
     ap.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra legs (roofline, fp32, sampling, config3, "
+                         "cpu_baseline, the exposed all-reduce time at N > 1); the --no-* options trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss.npy, params.npy) into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -70,7 +81,10 @@ def parse():
     ap.add_argument("--no-config3", action="store_true")
     ap.add_argument("--sample-steps", type=int, default=250,
                     help="DDPM steps of the sampling legs (config 4: 250)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the result is per timed step)")
+    return args
 
 
 def build(args, device):
@@ -87,6 +101,57 @@ def build(args, device):
     trainer = VideoDecoderTrainer(dec, lr=3e-4, wd=1e-2, use_ema=False, amp=args.dtype == "bf16",
                                   use_graphs=not getattr(args, "no_graphs", False))
     return dec, trainer
+
+
+DUMP_PARAM_SAMPLE = 8 << 20  # elements of params.npy (32 MB in f32)
+
+
+def training_state(trainer):
+    """An in-memory checkpoint (the layout of VideoDecoderTrainer.save) of the
+    trainer as built: the seeded weights, no AdamW moments, step 0."""
+    import copy
+    obj = dict(model={k: v.detach().clone() for k, v in trainer.decoder.state_dict().items()},
+               steps=trainer.steps.detach().clone())
+    for i in range(trainer.num_unets):
+        obj[f"optim{i}"] = copy.deepcopy(getattr(trainer, f"optim{i}").state_dict())
+        obj[f"sched{i}"] = copy.deepcopy(getattr(trainer, f"sched{i}").state_dict())
+    return obj
+
+
+def restore_training_state(trainer, state):
+    """VideoDecoderTrainer.load without the file: the flat buffers and the
+    captured graph stay, the packed weight images are rebuilt."""
+    from dalle2_video import ops
+    trainer.load_state_dict(state)
+    ops.PACK.refresh()
+
+
+def dump_outputs(out_dir, loss, unet):
+    """What a caller of the timed step holds after the last one, as .npy files:
+    loss.npy    the loss the last trainer call returned (f64, shape (1,))
+    params.npy  the unet's parameters after the last update(), f32, flattened
+                and concatenated in named_parameters() order; of more than
+                DUMP_PARAM_SAMPLE elements a fixed sample (indices drawn with
+                replacement from a generator seeded 0, the same in every run)
+    A training run amplifies the rounding differences of the kernels' float
+    atomics from step to step (1e-5 of the loss after one step, 1e-2 after
+    100), so with --dump-outputs the last timed step starts from the restored
+    initial state (main): every input of that step, the parameters and the
+    AdamW state included, is then the same in every run with the same
+    arguments, and two builds are comparable file by file to the rounding of
+    one step."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([float(loss)], dtype=np.float64))
+    with torch.no_grad():
+        flat = torch.cat([p.detach().float().reshape(-1) for _, p in unet.named_parameters()])
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            flat = flat[idx.to(flat.device)]
+        params = flat.cpu().numpy()
+    np.save(os.path.join(out_dir, "params.npy"), params)
+    log(f"outputs of the last timed step in {out_dir}: loss {float(loss):.6f}, {params.size} parameter values")
 
 
 def cpu_baseline(args):
@@ -517,10 +582,12 @@ def main():
     g = torch.Generator(device=device).manual_seed(1234 + rank)
     video = torch.rand(args.batch, 3, args.frames, args.size, args.size, device=device, generator=g)
     embed = torch.randn(args.batch, 512, device=device, generator=g)
+    initial = training_state(trainer) if args.dump_outputs else None
 
     def step():
-        trainer(video_embed=embed, video=video, unet_number=1)
+        loss = trainer(video_embed=embed, video=video, unet_number=1)
         trainer.update(1)
+        return loss
 
     # the trainer captures its HIP graph on the 4th call (the first update()
     # builds the flat gradient buffers, then two eager calls warm the pass):
@@ -534,19 +601,31 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    paused = 0.0
+    for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            # the dumped step computes from the initial state (dump_outputs);
+            # the restore is not a step's work: the clock stops for it
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            restore_training_state(trainer, initial)
+            torch.cuda.synchronize()
+            paused = time.perf_counter() - tp
+        loss = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
     if world > 1:
         te = torch.tensor([elapsed], device=device)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = te.item()
+    if args.dump_outputs and rank == 0:
+        # before any further step: the state the last timed step left
+        dump_outputs(args.dump_outputs, loss, dec.unets[0])
 
     exposed = None
-    if world > 1 and trainer.overlap is not None:
+    if args.full and world > 1 and trainer.overlap is not None:
         # the all-reduce time the backward does not hide: eager steps (the same
         # bucket schedule the captured graph replays), from the end of the
         # backward's compute to the join of every bucket, max over ranks
@@ -565,7 +644,7 @@ def main():
     kernels = None
     conv_shapes = None
     attention = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # live per-launch HIP-event timing of every conv kernel over K more steps
         from dalle2_video import ops
         ops.TIMER = ops.KernelTimer()
@@ -634,7 +713,7 @@ def main():
 
     log(f"train: {args.steps / elapsed:.2f} steps/s per GPU")
     fp32 = None
-    if not args.no_fp32 and args.dtype == "bf16" and world == 1:
+    if args.full and not args.no_fp32 and args.dtype == "bf16" and world == 1:
         # hand the cached blocks of the bf16 legs back first: on a cache the
         # bf16 step and the timer's closures have carved up, the f32 step ran
         # at 12.7-13.1 steps/s instead of 17.7-18.1 (r05, same box, same tree)
@@ -644,10 +723,10 @@ def main():
         fp32 = fp32_leg(args, device)
         log("fp32:", fp32["value"], "steps/s")
     sampling = None
-    if not args.no_sampling and world == 1:
+    if args.full and not args.no_sampling and world == 1:
         sampling = sampling_leg(args, device)
     config3 = None
-    if not args.no_config3 and world == 1:
+    if args.full and not args.no_config3 and world == 1:
         import gc
         gc.collect()
         torch.cuda.empty_cache()
@@ -655,7 +734,7 @@ def main():
         log(f"config3: {config3['value']} alternating steps/s")
 
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline on", args.cpu_threads or torch.get_num_threads(), "threads")
         base = cpu_baseline(args)
         log("cpu baseline:", base["value"], "steps/s")

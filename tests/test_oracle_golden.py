@@ -44,7 +44,7 @@ def _threads():
 
 
 def test_g1_blocks():
-    g = gold("g1_blocks")
+    g = {**gold("g1_blocks"), **gold("g1_blocks_2")}  # one fixture in two files (size)
     x, x3 = torch.from_numpy(g["x"]), torch.from_numpy(g["x3"])
     temb, cond = torch.from_numpy(g["temb"]), torch.from_numpy(g["cond"])
     cases = {
