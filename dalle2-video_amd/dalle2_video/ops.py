@@ -171,6 +171,41 @@ def window_ok(x0, x1, cin, c0, cout, ld0, ld1, ldy, ldres, ksize, h, w, nf, gn_P
             and x0.data_ptr() % 16 == 0 and (x1 is None or x1.data_ptr() % 16 == 0))
 
 
+def frame_tile(m, w, cout, gn=False):
+    """Mirror of launch_fwd_frame's tile choice (dv_conv.hip): (output channels
+    per workgroup, waves, tap split) of the window-form conv."""
+    tiles64 = (m // 128) * (cout // 64)
+    co = 32 if tiles64 <= 128 else 64
+    if w == 16 and co == 64 and not gn and cout % 128 == 0 and tiles64 > 256:
+        return 128, 8, False  # two 64-channel halves on 8 waves
+    if w == 8 and co == 64:
+        return 64, 8, True    # the tap split: two waves per SIMD
+    return co, 4, False
+
+
+def stripe_stages(m, h, w, cout):
+    """Mirror of launch_fwd_stripe (dv_conv.hip): 128-pixel stages per workgroup
+    of the resident-weight stripe conv (its row ring wraps from the fifth on)."""
+    nstages, ct = m // 128, cout // 64
+    bx = max(1, min(256 // ct, nstages))
+    spf = h // (128 // w)
+    sps = (nstages + bx - 1) // bx
+    if sps >= spf:
+        return spf
+    while spf % sps:
+        sps += 1
+    return sps
+
+
+def wgrad_split(m, cin, cout, ks):
+    """Mirror of stripe_split (dv_conv.hip): (stages per split, splits) of the
+    row-window / 1x1 wgrad; more than one split stores bf16 partials."""
+    nstages = m // 128
+    want = max(1, min((512 if ks == 1 else 256) // ((cout // 64) * (cin // 64)), nstages))
+    sps = (nstages + want - 1) // want
+    return sps, (nstages + sps - 1) // sps
+
+
 def _stripe_geom_ok(h, w):
     """Mirror of stripe_geom() in dv_conv.hip (128-pixel stage windows)."""
     if w not in (8, 16, 32, 64):
