@@ -712,6 +712,49 @@ __global__ void p_sample_kernel(const float* x, const T* eps, int ld, const floa
   }
 }
 
+// one DDIM step t -> t_next (p_sample_loop_ddim, dalle2_video.py:1811-1876).
+// The coefficients come from the two gathered alphas_cumprod entries, per
+// element in f32, so one captured graph serves every step of the loop.  Each
+// is written in the algebraically equal form that has no cancellation
+// (a = ac[t], an = ac[t_next], a < an):
+//   sqrt(1/a - 1)      = sqrt((1 - a)/a)           (1 - a is exact near a = 1)
+//   1 - a/an           = (an - a)/an
+//   (1 - an) - c1^2    = (1 - an) ((1 - eta^2) + eta^2 a (1 - an)/(an (1 - a)))
+//   pred_noise         = eps + (x0 - clamp(x0))/sqrt(1/a - 1)
+// (the literal (sqrt(1/a) x - x0)/sqrt(1/a - 1) loses ~1e-4 at t = 1).
+// t_next == 0 takes no noise and eta == 0 reads none (noise may be NULL).
+template <typename T>
+__global__ void ddim_step_kernel(const float* x, const T* eps, int ld, const float* noise,
+                                 const long long* t, const long long* t_next, const float* ac,
+                                 float eta, float* out, float* x0_out, int B, int C, int T_,
+                                 int HW, int clip, int nt) {
+  const long long n = (long long)B * C * T_ * HW;
+  GRID_STRIDE(i, n) {
+    const int hw = (int)(i % HW);
+    long long r = i / HW;
+    const int tt = (int)(r % T_);
+    r /= T_;
+    const int c = (int)(r % C), b = (int)(r / C);
+    const long long ti0 = t[b], tn0 = t_next[b];
+    // out-of-schedule pair: NaN, no OOB read
+    const bool ok = ti0 >= 0 && ti0 < nt && tn0 >= 0 && tn0 < ti0;
+    const long long ti = ok ? ti0 : 0, tn = ok ? tn0 : 0;
+    const float a = ac[ti], an = ac[tn];
+    const float sra = sqrtf(1.f / a), srm1 = sqrtf((1.f - a) / a);
+    const float e2 = eta * eta, om_an = 1.f - an;
+    const float c1 = eta * sqrtf((an - a) / an * om_an / (1.f - a));
+    const float c2 = sqrtf(om_an * ((1.f - e2) + e2 * (a * om_an / (an * (1.f - a)))));
+    const long long p = ((long long)b * T_ + tt) * HW + hw;
+    const float e = ld > 0 ? (float)eps[p * ld + c] : ((const float*)eps)[i];
+    const float x0u = sra * x[i] - srm1 * e;
+    const float x0 = clip ? fminf(fmaxf(x0u, -1.f), 1.f) : x0u;
+    const float pn = x0 != x0u ? e + (x0u - x0) / srm1 : e;
+    const float z = (eta != 0.f && tn != 0) ? noise[i] : 0.f;
+    out[i] = ok ? x0 * sqrtf(an) + c1 * z + c2 * pn : __builtin_nanf("");
+    if (x0_out) x0_out[i] = ok ? x0 : __builtin_nanf("");
+  }
+}
+
 
 // per-frame nearest resize of NCTHW f32 planes (F.interpolate(mode="nearest"),
 // resize_image_to at dalle2_video.py:2257, 1129-1146); optional clamp
@@ -944,6 +987,22 @@ extern "C" int dv_p_sample(int dtype, const float* x, const void* eps, int ld, c
            (p_sample_kernel<float><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, logvar, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
            (p_sample_kernel<bf16><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, logvar, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
   return check_launch("p_sample");
+}
+
+extern "C" int dv_ddim_step(int dtype, const float* x, const void* eps, int ld, const float* noise,
+                            const long long* t, const long long* t_next,
+                            const float* alphas_cumprod, float eta, float* out, float* x0_out,
+                            int B, int C, int T, int H, int W, int clip, int num_timesteps,
+                            void* stream) {
+  DV_REQUIRE(x && eps && t && t_next && alphas_cumprod && out && num_timesteps > 0, "bad arguments");
+  DV_REQUIRE(noise || eta == 0.f, "noise may be NULL only when eta == 0");
+  DV_REQUIRE(ld == 0 ? dtype == DV_F32 : ld >= C, "eps is NCTHW f32 (ld == 0) or channels-last with ld >= C");
+  const long long n = (long long)B * C * T * H * W;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           (ddim_step_kernel<float><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, t_next, alphas_cumprod, eta, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
+           (ddim_step_kernel<bf16><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, t_next, alphas_cumprod, eta, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
+  return check_launch("ddim_step");
 }
 
 extern "C" int dv_resize_nearest(const float* x, float* y, long long planes, int hin, int win,

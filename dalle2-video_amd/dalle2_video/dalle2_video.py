@@ -894,8 +894,19 @@ class LowresVideoConditioner(nn.Module):
 
 
 # ---------------------------------------------------------------------------
-# one DDPM denoise step as a replayable HIP graph (sampling loop, config 4)
+# one denoise step (DDPM or DDIM) as a replayable HIP graph (sampling loop, config 4)
 # ---------------------------------------------------------------------------
+
+
+def ddim_time_pairs(total_timesteps, sampling_timesteps):
+    """The (time, time_next) pairs of a DDIM run of `sampling_timesteps` steps
+    over a `total_timesteps` schedule (dalle2_video.py:1787-1791): S + 2 evenly
+    spaced points on [0, T] without the last, truncated to int, walked
+    downwards; pairs that truncate to the same step are dropped.  The last
+    pair ends at 0."""
+    times = torch.linspace(0.0, total_timesteps, steps=sampling_timesteps + 2)[:-1]
+    times = list(reversed(times.int().tolist()))
+    return [(t, tn) for t, tn in zip(times[:-1], times[1:]) if t > tn]
 
 
 class _DenoiseStepGraph:
@@ -905,18 +916,33 @@ class _DenoiseStepGraph:
     allocated workspace exists afterwards), the third captures the step —
     Unet3D forward (two with classifier-free guidance), `randn_like` noise on
     the device generator and the posterior update written back into x — and
-    every call from then on sets t and replays the graph."""
+    every call from then on sets t and replays the graph.
+
+    ddim_eta=None is that DDPM step.  A float makes the update the DDIM step
+    t -> t_next (ops.ddim_step; the loop at :1811-1876) with a second device
+    buffer `t_next`; at eta == 0 the step draws no noise."""
 
     EAGER_CALLS = 2
 
     def __init__(self, decoder, unet, x, video_embed, noise_scheduler, cond_scale, lowres_cond_vid,
-                 clip_denoised):
+                 clip_denoised, ddim_eta=None):
         self.decoder, self.unet, self.x = decoder, unet, x
         self.video_embed, self.sched, self.cond_scale = video_embed, noise_scheduler, cond_scale
         self.lowres, self.clip = lowres_cond_vid, clip_denoised
         self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
+        self.ddim_eta = ddim_eta
+        self.t_next = torch.zeros_like(self.t) if exists(ddim_eta) else None
         self.calls = 0
         self.graph = None
+
+    def _ddpm_update(self, eps):
+        noise = torch.randn_like(self.x)
+        ops.p_sample_step(self.x, eps, noise, self.t, self.sched, self.clip, out=self.x, want_x0=False)
+
+    def _ddim_update(self, eps):
+        noise = torch.randn_like(self.x) if self.ddim_eta != 0 else None
+        ops.ddim_step(self.x, eps, noise, self.t, self.t_next, self.sched, self.ddim_eta, self.clip,
+                      out=self.x, want_x0=False)
 
     def _body(self):
         x, unet = self.x, self.unet
@@ -931,11 +957,13 @@ class _DenoiseStepGraph:
             eps = unet.forward_with_cond_scale(x, self.t, video_embed=self.video_embed,
                                                cond_scale=self.cond_scale,
                                                lowres_cond_video=self.lowres)
-        noise = torch.randn_like(x)
-        ops.p_sample_step(x, eps, noise, self.t, self.sched, self.clip, out=x, want_x0=False)
+        # (no bound method kept on self: `del step` must free the graph at once)
+        (self._ddim_update if exists(self.ddim_eta) else self._ddpm_update)(eps)
 
-    def __call__(self, time):
+    def __call__(self, time, time_next=None):
         self.t.fill_(time)
+        if exists(self.t_next):
+            self.t_next.fill_(time_next)
         self.calls += 1
         if self.calls <= self.EAGER_CALLS or ops.TIMER is not None:
             self._body()
@@ -1272,14 +1300,70 @@ class VideoDecoder(nn.Module):
         return self.unnormalize_video(vid)
 
     @torch.no_grad()
+    def p_sample_ddim(self, unet, x, t, t_next, video_embed, noise_scheduler, eta, cond_scale=1.0,
+                      lowres_cond_vid=None, clip_denoised=True, noise=None):
+        """One DDIM step t -> t_next (the body of the loop at
+        dalle2_video.py:1811-1876): returns (x_next, x0).  At eta == 0 no noise
+        is drawn."""
+        assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
+        pred = unet.forward_with_cond_scale(x, t, video_embed=video_embed,
+                                            cond_scale=cond_scale,
+                                            lowres_cond_video=lowres_cond_vid)
+        if eta != 0:
+            noise = default(noise, lambda: torch.randn_like(x))
+        return ops.ddim_step(x, pred, noise, t, t_next, noise_scheduler, eta, clip_denoised)
+
+    @torch.no_grad()
+    def p_sample_loop_ddim(self, unet, shape, video_embed, noise_scheduler, timesteps, eta=1.0,
+                           predict_x_start=False, predict_v=False, learned_variance=False,
+                           clip_denoised=True, lowres_cond_vid=None, text_encodings=None,
+                           cond_scale=1, is_latent_diffusion=False, lowres_noise_level=None,
+                           init_noise=None):
+        """dalle2_video.py:1758-1889 with the keyword names Unet3D has (SURVEY
+        Q2: the reference passes image_embed= / lowres_cond_img= and raises):
+        one Unet3D forward and one ops.ddim_step per pair of ddim_time_pairs.
+        As in the reference, `eta` is overwritten by self.ddim_sampling_eta.
+        At eta == 0 no noise is drawn at all, eager or captured: c1 = 0 makes
+        the draw dead, and there is no reference RNG stream to match (its loop
+        never ran).  init_noise (optional) is the start tensor instead of a
+        fresh draw.  On the GPU the steps after the first two replay one
+        captured HIP graph, as in p_sample_loop_ddpm."""
+        assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
+        b, eta = shape[0], self.ddim_sampling_eta
+        pairs = ddim_time_pairs(noise_scheduler.num_timesteps, timesteps)
+        if exists(init_noise):
+            assert tuple(init_noise.shape) == tuple(shape)
+            vid = init_noise.to(device=self.device, dtype=torch.float32).clone()
+        else:
+            vid = torch.randn(shape, device=self.device)
+        if not is_latent_diffusion:
+            lowres_cond_vid = maybe(self.normalize_video)(lowres_cond_vid)
+        if vid.is_cuda and self.sample_graphs:
+            with ops.private_pack_cache():
+                step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
+                                         lowres_cond_vid, clip_denoised, ddim_eta=eta)
+                for time, time_next in pairs:
+                    step(time, time_next)
+                del step
+            return self.unnormalize_video(vid)
+        with (ops.private_pack_cache() if vid.is_cuda else nullcontext()):
+            for time, time_next in pairs:
+                times = torch.full((b,), time, device=self.device, dtype=torch.long)
+                times_next = torch.full((b,), time_next, device=self.device, dtype=torch.long)
+                vid, _ = self.p_sample_ddim(unet, vid, times, times_next, video_embed=video_embed,
+                                            noise_scheduler=noise_scheduler, eta=eta,
+                                            cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
+                                            clip_denoised=clip_denoised)
+        return self.unnormalize_video(vid)
+
+    @torch.no_grad()
     def p_sample_loop(self, *args, noise_scheduler, timesteps=None, **kwargs):
         num_timesteps = noise_scheduler.num_timesteps
         timesteps = default(timesteps, num_timesteps)
         assert timesteps <= num_timesteps
         if timesteps < num_timesteps:
-            # the reference DDIM path raises TypeError for Unet3D
-            raise TypeError("p_sample_loop_ddim is broken for Unet3D in the reference "
-                            "(image_embed= / lowres_cond_img= keywords, dalle2_video.py:1832-1841)")
+            return self.p_sample_loop_ddim(*args, noise_scheduler=noise_scheduler,
+                                           timesteps=timesteps, **kwargs)
         return self.p_sample_loop_ddpm(*args, noise_scheduler=noise_scheduler, **kwargs)
 
     @torch.no_grad()

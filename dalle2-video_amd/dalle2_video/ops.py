@@ -2515,6 +2515,45 @@ def p_sample_step(x, eps, noise, times, sched, clip_denoised=True, out=None, wan
     return out, x0
 
 
+def ddim_step(x, eps, noise, times, times_next, sched, eta, clip_denoised=True, out=None, want_x0=True):
+    """One DDIM step times -> times_next (p_sample_loop_ddim,
+    dalle2_video.py:1811-1876): x0 as in p_sample_step, then
+    x0 sqrt(ac[t_next]) + c1 z + c2 pred_noise with c1 = eta sqrt((1 - a/an)
+    (1 - an)/(1 - a)), c2 = sqrt((1 - an) - c1^2).  The kernel derives every
+    coefficient from sched.alphas_cumprod.  eps and `out` as p_sample_step;
+    noise may be None when eta == 0 (c1 = 0: the draw would be dead)."""
+    require_gpu(x, eps, noise, times, times_next)
+    eta = float(eta)
+    if noise is None and eta != 0.0:
+        raise _lib.DVError("ddim_step: noise may be None only when eta == 0")
+    xf = x.float().contiguous()
+    nz = None if noise is None else noise.float().contiguous()
+    t = times.to(torch.int64).contiguous()
+    tn = times_next.to(torch.int64).contiguous()
+    B, C, T, H, W = xf.shape
+    if t.numel() != B or tn.numel() != B or (nz is not None and nz.shape != xf.shape):
+        raise _lib.DVError("ddim_step: times / times_next hold one entry per sample, noise is shaped like x")
+    if eps.dim() == 5:
+        ef = eps.float().contiguous()
+        ld, edt = 0, _lib.DV_F32
+        if ef.shape != xf.shape:
+            raise _lib.DVError(f"ddim_step: eps {tuple(eps.shape)} does not match x {tuple(xf.shape)}")
+    else:
+        ef = eps
+        ld, edt = cl_ld(eps), dt(eps)
+        if eps.shape[0] != B * T or tuple(eps.shape[1:3]) != (H, W) or eps.shape[-1] < C:
+            raise _lib.DVError(f"ddim_step: eps {tuple(eps.shape)} does not match x {tuple(xf.shape)}")
+    if out is None:
+        out = torch.empty_like(xf)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != xf.shape:
+        raise _lib.DVError("ddim_step: out must be a contiguous f32 tensor shaped like x")
+    x0 = torch.empty_like(xf) if want_x0 else None
+    call("dv_ddim_step", edt, ptr(xf), ptr(ef), ld, ptr(nz), ptr(t), ptr(tn), ptr(sched.alphas_cumprod),
+         ctypes_float(eta), ptr(out), ptr(x0), B, C, T, H, W, int(clip_denoised),
+         sched.alphas_cumprod.numel(), stream())
+    return out, x0
+
+
 def resize_nearest(video, size, clamp_range=None):
     """Per-frame nearest resize of an NCTHW clip to size x size."""
     require_gpu(video)

@@ -431,6 +431,20 @@ int dv_p_sample(int dtype, const float* x, const void* eps, int ld, const float*
                 const float* coef1, const float* coef2, const float* logvar, float* out,
                 float* x0_out, int B, int C, int T, int H, int W, int clip, int num_timesteps,
                 void* stream);
+/* one DDIM step t[b] -> t_next[b] (VideoDecoder.p_sample_loop_ddim,
+ * :1811-1876): with a = alphas_cumprod[t], an = alphas_cumprod[t_next],
+ *   x0  = sqrt(1/a) x - sqrt(1/a - 1) eps          (clamped when clip != 0)
+ *   c1  = eta sqrt((1 - a/an)(1 - an)/(1 - a)),  c2 = sqrt((1 - an) - c1^2)
+ *   out = sqrt(an) x0 + c1 noise + c2 (sqrt(1/a) x - x0)/sqrt(1/a - 1)
+ * x, eps, out, x0_out as dv_p_sample (out may be x).  The coefficients are
+ * computed on the device from the f32 alphas_cumprod table (num_timesteps
+ * entries), so a captured call serves every step by rewriting t / t_next.
+ * A sample with t_next == 0 takes no noise; noise may be NULL when eta == 0.
+ * t or t_next outside [0, num_timesteps) or t_next >= t: that sample is NaN. */
+int dv_ddim_step(int dtype, const float* x, const void* eps, int ld, const float* noise,
+                 const long long* t, const long long* t_next, const float* alphas_cumprod,
+                 float eta, float* out, float* x0_out, int B, int C, int T, int H, int W,
+                 int clip, int num_timesteps, void* stream);
 
 /* ---- time conditioning MLPs (Unet3D.to_time_hiddens / to_time_tokens /
  * to_time_cond, dalle2_video.py:348-357; ResnetBlock3D.time_mlp, :152-155)
