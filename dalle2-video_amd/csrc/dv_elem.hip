@@ -18,6 +18,10 @@ int grid_for(long long work, int per_block = 256, int cap = 16384) {
   return (int)b;
 }
 
+bool objective_ok(int objective) {
+  return objective == DV_OBJ_EPS || objective == DV_OBJ_X0 || objective == DV_OBJ_V;
+}
+
 #define GRID_STRIDE(i, n) \
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
 
@@ -252,6 +256,228 @@ __global__ void mse_bwd_kernel(const T* pred, int ld, const float* target, int B
       const float d = (float)pred[p * ld + c] - target[(((long long)b * C + c) * T_ + tt) * HW + hw];
       dp[p * lddp + c] = (T)(2.f * g * wb * d);
     }
+  }
+}
+
+// l2 loss against the x0 / v target of p_losses (dalle2_video.py:1988-1995),
+// formed per element from the NCTHW x_start and noise (no target tensor):
+//   x0: target = xs            v: target = sqrt(a) noise - sqrt(1 - a) xs
+// xs is what q_sample_kernel noised (2 x_start - 1 when `normalize`).  The trip
+// shape, reduction order and single atomic per block are mse_kernel's; a
+// timestep outside the schedule gives a NaN target and reads no table entry.
+template <int OBJ>
+__device__ __forceinline__ float loss_target(float xs0, float nz, int normalize, float a, float s) {
+  const float xs = normalize ? xs0 * 2.f - 1.f : xs0;
+  if constexpr (OBJ == DV_OBJ_V) return a * nz - s * xs;
+  else return a != a ? a : xs;  // a is NaN for an out-of-schedule t
+}
+
+template <typename T, int OBJ>
+__global__ __launch_bounds__(256) void diff_loss_kernel(const T* pred, int ld, const float* x0,
+                                                        const float* noise, const long long* t,
+                                                        const float* sa, const float* s1m, int B,
+                                                        int C, int T_, int HW, int normalize, int nt,
+                                                        const float* w, float* loss, float scale) {
+  __shared__ float sh[4];
+  const long long npix = (long long)B * T_ * HW;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  float acc = 0.f;
+  for (long long p0 = (long long)blockIdx.x * blockDim.x + threadIdx.x; p0 < npix; p0 += 4 * stride) {
+    long long pp[4];
+    long long tb[4];
+    float wb[4], ka[4], ks[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long p = p0 + u * stride;
+      const bool live = p < npix;
+      pp[u] = live ? p : p0;
+      const int hw = (int)(pp[u] % HW);
+      const long long ft = pp[u] / HW;
+      const int tt = (int)(ft % T_), b = (int)(ft / T_);
+      tb[u] = ((long long)b * C * T_ + tt) * HW + hw;  // channel 0 of this pixel in the NCTHW tensors
+      wb[u] = live ? (w ? w[b] : 1.f) : 0.f;
+      const long long ti = t[b];
+      const bool ok = ti >= 0 && ti < nt;
+      ka[u] = ok ? sa[ti] : __builtin_nanf("");
+      ks[u] = ok ? s1m[ti] : __builtin_nanf("");
+    }
+    for (int c = 0; c < C; ++c) {
+      float d[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long long i = tb[u] + (long long)c * T_ * HW;
+        d[u] = (float)pred[pp[u] * ld + c] - loss_target<OBJ>(x0[i], noise[i], normalize, ka[u], ks[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc += wb[u] * d[u] * d[u];
+    }
+  }
+  acc = block_sum<256>(acc, sh);
+  if (threadIdx.x == 0) atomicAdd(loss, acc * scale);
+}
+
+template <typename T, int OBJ>
+__global__ void diff_loss_bwd_kernel(const T* pred, int ld, const float* x0, const float* noise,
+                                     const long long* t, const float* sa, const float* s1m, int B,
+                                     int C, int T_, int HW, int normalize, int nt, const float* w,
+                                     const float* dloss, float scale, T* dp, int lddp) {
+  const long long npix = (long long)B * T_ * HW;
+  const float g = dloss[0] * scale;
+  GRID_STRIDE(p, npix) {
+    const int hw = (int)(p % HW);
+    const long long ft = p / HW;
+    const int tt = (int)(ft % T_), b = (int)(ft / T_);
+    const float wb = w ? w[b] : 1.f;
+    const long long ti = t[b];
+    const bool ok = ti >= 0 && ti < nt;
+    const float ka = ok ? sa[ti] : __builtin_nanf(""), ks = ok ? s1m[ti] : __builtin_nanf("");
+    for (int c = 0; c < C; ++c) {
+      const long long i = (((long long)b * C + c) * T_ + tt) * HW + hw;
+      const float d = (float)pred[p * ld + c] - loss_target<OBJ>(x0[i], noise[i], normalize, ka, ks);
+      dp[p * lddp + c] = (T)(2.f * g * wb * d);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// dynamic thresholding (dynamic_threshold, dalle2_video.py:1531-1549):
+//   s[b] = max(1, quantile(|x0_u[b]|, p))  with torch.quantile's linear
+// interpolation: position p (N - 1) = k0 + frac (split on the host in f64),
+// s = v[k0] + frac (v[k0 + 1] - v[k0]) over the order statistics v of the
+// sample's N = C T H W magnitudes.  x0_u is recomputed from (x, pred, t,
+// objective) in every pass; nothing but s[b] is written.
+//
+// One workgroup per sample, so nothing waits on another workgroup and the
+// only state is LDS.  v[k0] is found exactly by a radix select over the bit
+// patterns of the magnitudes (for non-negative floats the unsigned order of
+// the patterns is the order of the values): three passes over 11 + 10 + 10
+// bits, each a 2048-bin LDS histogram of the elements that match the prefix
+// chosen so far, a block-wide scan of the bins, and the bin holding the
+// remaining rank.  The last bin is one value; if it holds more elements than
+// the remaining rank + 1, v[k0 + 1] is that value as well, otherwise a fourth
+// pass takes the minimum pattern above it.  Integer counts only: the result
+// does not depend on the order the atomics land in.  A magnitude that is not
+// finite (or an out-of-schedule t) makes s[b] NaN.
+// ---------------------------------------------------------------------------
+constexpr int DT_THREADS = 1024, DT_BINS = 2048;
+
+// (kx, kp) of x0_u = kx x - kp pred.  kp_tab == NULL: kx_tab is alphas_cumprod
+// and the pair is derived as ddim_step_kernel derives it; otherwise the two
+// gathered tables of p_sample_kernel.
+template <int OBJ>
+__device__ __forceinline__ void x0_coefs(const float* kx_tab, const float* kp_tab, long long ti,
+                                         float& kx, float& kp) {
+  if constexpr (OBJ == DV_OBJ_X0) {
+    kx = 0.f;
+    kp = -1.f;
+  } else if (kp_tab) {
+    kx = kx_tab[ti];
+    kp = kp_tab[ti];
+  } else {
+    const float a = kx_tab[ti];
+    if constexpr (OBJ == DV_OBJ_EPS) {
+      kx = sqrtf(1.f / a);
+      kp = sqrtf((1.f - a) / a);
+    } else {
+      kx = sqrtf(a);
+      kp = sqrtf(1.f - a);
+    }
+  }
+}
+
+template <typename T, int OBJ>
+__global__ __launch_bounds__(DT_THREADS) void dyn_thres_kernel(const float* x, const T* pred, int ld,
+                                                              const long long* t, const float* kx_tab,
+                                                              const float* kp_tab, int C, int T_,
+                                                              int HW, int nt, long long k0,
+                                                              float frac, float* s_out) {
+  __shared__ unsigned hist[DT_BINS];
+  __shared__ unsigned wsum[DT_THREADS / 64];
+  __shared__ unsigned sel_bin, sel_rank, sel_cnt, bad, next_min;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const long long ti = t[b];
+  if (ti < 0 || ti >= nt) {  // uniform over the workgroup
+    if (tid == 0) s_out[b] = __builtin_nanf("");
+    return;
+  }
+  float kx, kp;
+  x0_coefs<OBJ>(kx_tab, kp_tab, ti, kx, kp);
+  const int npix = T_ * HW;  // host: C * npix < 2^31
+  const float* xb = x + (long long)b * C * npix;
+  // |x0_u| of channel c at pixel q of this sample, as its bit pattern
+  auto mag = [&](int q, int c) -> unsigned {
+    const float xv = xb[(long long)c * npix + q];
+    const float e = ld > 0 ? (float)pred[((long long)b * npix + q) * ld + c]
+                           : ((const float*)pred)[((long long)b * C + c) * npix + q];
+    float x0u;
+    if constexpr (OBJ == DV_OBJ_X0) x0u = e;
+    else x0u = kx * xv - kp * e;
+    return __float_as_uint(x0u) & 0x7fffffffu;
+  };
+  if (tid == 0) {
+    bad = 0u;
+    next_min = 0xffffffffu;
+  }
+  unsigned prefix = 0u, prefix_mask = 0u, rank = (unsigned)k0, cnt_eq = 0u;
+  constexpr int SHIFT[3] = {20, 10, 0}, NBITS[3] = {11, 10, 10};
+#pragma unroll
+  for (int pass = 0; pass < 3; ++pass) {
+    for (int i = tid; i < DT_BINS; i += DT_THREADS) hist[i] = 0u;
+    __syncthreads();
+    const unsigned bin_mask = (1u << NBITS[pass]) - 1u;
+    bool nonfinite = false;
+    for (int q = tid; q < npix; q += DT_THREADS) {
+      for (int c = 0; c < C; ++c) {
+        const unsigned m = mag(q, c);
+        nonfinite |= m >= 0x7f800000u;
+        if ((m & prefix_mask) == prefix) atomicAdd(&hist[(m >> SHIFT[pass]) & bin_mask], 1u);
+      }
+    }
+    if (pass == 0 && nonfinite) bad = 1u;  // (any writer stores the same value)
+    __syncthreads();
+    // inclusive scan of the bins, two per thread
+    const unsigned h0 = hist[2 * tid], h1 = hist[2 * tid + 1];
+    unsigned incl = h0 + h1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned up = __shfl_up(incl, o, 64);
+      if ((tid & 63) >= o) incl += up;
+    }
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    unsigned base = 0u;
+    for (int w = 0; w < (tid >> 6); ++w) base += wsum[w];
+    const unsigned excl = base + incl - (h0 + h1);
+    if (rank >= excl && rank < excl + h0 + h1) {  // exactly one thread: the counts sum to > rank
+      const bool second = rank >= excl + h0;
+      sel_bin = 2 * tid + (second ? 1 : 0);
+      sel_rank = rank - excl - (second ? h0 : 0u);
+      sel_cnt = second ? h1 : h0;
+    }
+    __syncthreads();
+    prefix |= sel_bin << SHIFT[pass];
+    prefix_mask |= bin_mask << SHIFT[pass];
+    rank = sel_rank;
+    cnt_eq = sel_cnt;
+    __syncthreads();  // sel_* and hist are rewritten by the next pass
+  }
+  // prefix is v[k0]; cnt_eq elements equal it and `rank` of them sort below k0
+  unsigned hi = prefix;
+  if (frac > 0.f && rank + 1 >= cnt_eq) {  // v[k0 + 1] is the next larger value (uniform branch)
+    unsigned mn = 0xffffffffu;
+    for (int q = tid; q < npix; q += DT_THREADS)
+      for (int c = 0; c < C; ++c) {
+        const unsigned m = mag(q, c);
+        if (m > prefix && m < mn) mn = m;
+      }
+    atomicMin(&next_min, mn);
+    __syncthreads();
+    hi = next_min;
+  }
+  if (tid == 0) {
+    const float v0 = __uint_as_float(prefix), v1 = __uint_as_float(hi);
+    const float qv = frac > 0.f ? v0 + frac * (v1 - v0) : v0;
+    s_out[b] = bad ? __builtin_nanf("") : fmaxf(qv, 1.f);
   }
 }
 
@@ -686,11 +912,36 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* part, int n
   coef[1] = norm;
 }
 
-template <typename T>
+// objective of the network output (VideoDecoder predict_x_start / predict_v)
+constexpr int OBJ_EPS = DV_OBJ_EPS, OBJ_X0 = DV_OBJ_X0, OBJ_V = DV_OBJ_V;
+
+// thresholding of the derived x0 (dynamic_threshold, dalle2_video.py:1531-1549).
+// DYN = false is the eps step with the static clamp, compiled as it was before
+// the objectives existed.  Every other combination runs DYN = true:
+// clamp(x0, -s, s)/s with the per-sample s of dyn_thres_kernel (s >= 1; a NaN s
+// poisons the sample through the division), s = 1 when dyn_s is NULL.  Static
+// and dynamic thresholding of one objective are therefore the same
+// instructions, and a sample whose s is 1 comes out to the bit as under the
+// static clamp (x/1 is exact).
+template <bool DYN>
+__device__ __forceinline__ float threshold_x0(float x0, const float* dyn_s, int b) {
+  if constexpr (DYN) {
+    const float s = dyn_s ? dyn_s[b] : 1.f;
+    return fminf(fmaxf(x0, -s), s) / s;
+  } else {
+    return fminf(fmaxf(x0, -1.f), 1.f);
+  }
+}
+
+// x0 = kx[t] x - kp[t] pred with (kx, kp) = (sqrt(1/a), sqrt(1/a - 1)) for the
+// eps objective and (sqrt(a), sqrt(1 - a)) for v (NoiseScheduler's
+// predict_start_from_v); the x0 objective takes pred itself and reads neither
+template <typename T, int OBJ, bool DYN>
 __global__ void p_sample_kernel(const float* x, const T* eps, int ld, const float* noise,
                                 const long long* t, const float* sra, const float* srm1,
-                                const float* c1, const float* c2, const float* logvar, float* out,
-                                float* x0_out, int B, int C, int T_, int HW, int clip, int nt) {
+                                const float* c1, const float* c2, const float* logvar,
+                                const float* dyn_s, float* out, float* x0_out, int B, int C, int T_,
+                                int HW, int clip, int nt) {
   const long long n = (long long)B * C * T_ * HW;
   GRID_STRIDE(i, n) {
     const int hw = (int)(i % HW);
@@ -703,8 +954,10 @@ __global__ void p_sample_kernel(const float* x, const T* eps, int ld, const floa
     const long long ti = ok ? ti0 : 0;
     const long long p = ((long long)b * T_ + tt) * HW + hw;
     const float e = ld > 0 ? (float)eps[p * ld + c] : ((const float*)eps)[i];
-    float x0 = sra[ti] * x[i] - srm1[ti] * e;
-    if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    float x0;
+    if constexpr (OBJ == OBJ_X0) x0 = e;
+    else x0 = sra[ti] * x[i] - srm1[ti] * e;
+    if (clip) x0 = threshold_x0<DYN>(x0, dyn_s, b);
     const float mean = c1[ti] * x0 + c2[ti] * x[i];
     const float nz = ti == 0 ? 0.f : 1.f;
     out[i] = ok ? mean + nz * expf(0.5f * logvar[ti]) * noise[i] : __builtin_nanf("");
@@ -722,12 +975,19 @@ __global__ void p_sample_kernel(const float* x, const T* eps, int ld, const floa
 //   (1 - an) - c1^2    = (1 - an) ((1 - eta^2) + eta^2 a (1 - an)/(an (1 - a)))
 //   pred_noise         = eps + (x0 - clamp(x0))/sqrt(1/a - 1)
 // (the literal (sqrt(1/a) x - x0)/sqrt(1/a - 1) loses ~1e-4 at t = 1).
+// The other objectives give the unthresholded x0_u and the noise e_u it implies
+// in the same cancellation-free way:
+//   v :  x0_u = sqrt(a) x - sqrt(1 - a) v,   e_u = sqrt(1 - a) x + sqrt(a) v
+//   x0:  x0_u = pred,                         e_u = (x - sqrt(a) pred)/sqrt(1 - a)
+//        (its cancellation near t = 0 belongs to the objective: the network
+//        output itself carries the noise only as that small difference)
+//   pred_noise = e_u + (x0_u - x0)/sqrt(1/a - 1)   wherever thresholding moved x0
 // t_next == 0 takes no noise and eta == 0 reads none (noise may be NULL).
-template <typename T>
+template <typename T, int OBJ, bool DYN>
 __global__ void ddim_step_kernel(const float* x, const T* eps, int ld, const float* noise,
                                  const long long* t, const long long* t_next, const float* ac,
-                                 float eta, float* out, float* x0_out, int B, int C, int T_,
-                                 int HW, int clip, int nt) {
+                                 float eta, const float* dyn_s, float* out, float* x0_out, int B,
+                                 int C, int T_, int HW, int clip, int nt) {
   const long long n = (long long)B * C * T_ * HW;
   GRID_STRIDE(i, n) {
     const int hw = (int)(i % HW);
@@ -746,15 +1006,25 @@ __global__ void ddim_step_kernel(const float* x, const T* eps, int ld, const flo
     const float c2 = sqrtf(om_an * ((1.f - e2) + e2 * (a * om_an / (an * (1.f - a)))));
     const long long p = ((long long)b * T_ + tt) * HW + hw;
     const float e = ld > 0 ? (float)eps[p * ld + c] : ((const float*)eps)[i];
-    const float x0u = sra * x[i] - srm1 * e;
-    const float x0 = clip ? fminf(fmaxf(x0u, -1.f), 1.f) : x0u;
-    const float pn = x0 != x0u ? e + (x0u - x0) / srm1 : e;
+    float x0u, eu;
+    if constexpr (OBJ == OBJ_EPS) {
+      x0u = sra * x[i] - srm1 * e;
+      eu = e;
+    } else if constexpr (OBJ == OBJ_V) {
+      const float sa = sqrtf(a), s1m = sqrtf(1.f - a);
+      x0u = sa * x[i] - s1m * e;
+      eu = s1m * x[i] + sa * e;
+    } else {
+      x0u = e;
+      eu = (x[i] - sqrtf(a) * e) / sqrtf(1.f - a);
+    }
+    const float x0 = clip ? threshold_x0<DYN>(x0u, dyn_s, b) : x0u;
+    const float pn = x0 != x0u ? eu + (x0u - x0) / srm1 : eu;
     const float z = (eta != 0.f && tn != 0) ? noise[i] : 0.f;
     out[i] = ok ? x0 * sqrtf(an) + c1 * z + c2 * pn : __builtin_nanf("");
     if (x0_out) x0_out[i] = ok ? x0 : __builtin_nanf("");
   }
 }
-
 
 // per-frame nearest resize of NCTHW f32 planes (F.interpolate(mode="nearest"),
 // resize_image_to at dalle2_video.py:2257, 1129-1146); optional clamp
@@ -917,6 +1187,60 @@ extern "C" int dv_mse_loss_bwd(int dtype, const void* pred, int ld, const float*
   return check_launch("mse_loss_bwd");
 }
 
+extern "C" int dv_diffusion_loss(int dtype, const void* pred, int ld, const float* x_start,
+                                 const float* noise, const long long* t, const float* sqrt_ac,
+                                 const float* sqrt_1m_ac, int B, int C, int T, int H, int W,
+                                 int normalize, int objective, int num_timesteps,
+                                 const float* sample_w, float* loss, void* stream) {
+  DV_REQUIRE(pred && x_start && noise && t && sqrt_ac && sqrt_1m_ac && loss && num_timesteps > 0,
+             "bad arguments");
+  DV_REQUIRE(objective_ok(objective), "objective is DV_OBJ_EPS, DV_OBJ_X0 or DV_OBJ_V");
+  // the eps target is the noise tensor as it stands: the plain l2 kernel
+  if (objective == DV_OBJ_EPS) return dv_mse_loss(dtype, pred, ld, noise, B, C, T, H, W, sample_w, loss, stream);
+  DV_REQUIRE(dtype == DV_F32 || dtype == DV_BF16, "unknown dtype");
+  const long long npix = (long long)B * T * H * W;
+  const float scale = 1.f / (float)((double)B * C * T * H * W);
+  hipStream_t st = (hipStream_t)stream;
+  zero_f32(loss, 1, st);
+  const int g = grid_for((npix + 3) / 4, 256, 256);
+#define DV_DL(TT, OBJ) diff_loss_kernel<TT, OBJ><<<g, 256, 0, st>>>((const TT*)pred, ld, x_start, noise, t, \
+    sqrt_ac, sqrt_1m_ac, B, C, T, H * W, normalize, num_timesteps, sample_w, loss, scale)
+  if (objective == DV_OBJ_X0) {
+    if (dtype == DV_F32) DV_DL(float, DV_OBJ_X0); else DV_DL(bf16, DV_OBJ_X0);
+  } else {
+    if (dtype == DV_F32) DV_DL(float, DV_OBJ_V); else DV_DL(bf16, DV_OBJ_V);
+  }
+#undef DV_DL
+  return check_launch("diffusion_loss");
+}
+
+extern "C" int dv_diffusion_loss_bwd(int dtype, const void* pred, int ld, const float* x_start,
+                                     const float* noise, const long long* t, const float* sqrt_ac,
+                                     const float* sqrt_1m_ac, int B, int C, int T, int H, int W,
+                                     int normalize, int objective, int num_timesteps,
+                                     const float* sample_w, const float* dloss, void* dpred,
+                                     int lddp, void* stream) {
+  DV_REQUIRE(pred && x_start && noise && t && sqrt_ac && sqrt_1m_ac && dloss && dpred &&
+                 num_timesteps > 0, "bad arguments");
+  DV_REQUIRE(objective_ok(objective), "objective is DV_OBJ_EPS, DV_OBJ_X0 or DV_OBJ_V");
+  if (objective == DV_OBJ_EPS)
+    return dv_mse_loss_bwd(dtype, pred, ld, noise, B, C, T, H, W, sample_w, dloss, dpred, lddp, stream);
+  DV_REQUIRE(dtype == DV_F32 || dtype == DV_BF16, "unknown dtype");
+  const long long npix = (long long)B * T * H * W;
+  const float scale = 1.f / (float)((double)B * C * T * H * W);
+  hipStream_t st = (hipStream_t)stream;
+#define DV_DLB(TT, OBJ) diff_loss_bwd_kernel<TT, OBJ><<<grid_for(npix), 256, 0, st>>>((const TT*)pred, ld, \
+    x_start, noise, t, sqrt_ac, sqrt_1m_ac, B, C, T, H * W, normalize, num_timesteps, sample_w, dloss, scale, \
+    (TT*)dpred, lddp)
+  if (objective == DV_OBJ_X0) {
+    if (dtype == DV_F32) DV_DLB(float, DV_OBJ_X0); else DV_DLB(bf16, DV_OBJ_X0);
+  } else {
+    if (dtype == DV_F32) DV_DLB(float, DV_OBJ_V); else DV_DLB(bf16, DV_OBJ_V);
+  }
+#undef DV_DLB
+  return check_launch("diffusion_loss_bwd");
+}
+
 extern "C" int dv_sinusoidal(const long long* t, const float* freqs, float* out, int B, int dim,
                              void* stream) {
   DV_REQUIRE(t && freqs && out && dim >= 4 && dim % 2 == 0, "bad arguments");
@@ -975,6 +1299,43 @@ extern "C" int dv_grad_clip_coef(const float* g, long long n, float max_norm, fl
   return check_launch("grad_clip_coef");
 }
 
+// launches one instantiation of an update kernel: K(T, OBJ, DYN) is the launch.
+// eps with the static clamp is the kernel of dv_p_sample / dv_ddim_step
+#define DV_UPDATE_DISPATCH(K)                                   \
+  do {                                                          \
+    if (dtype != DV_F32 && dtype != DV_BF16) DV_REQUIRE(false, "unknown dtype"); \
+    const bool f32 = dtype == DV_F32;                           \
+    if (objective == DV_OBJ_EPS && !dyn_s) {                    \
+      if (f32) K(float, DV_OBJ_EPS, false); else K(bf16, DV_OBJ_EPS, false); \
+    } else if (objective == DV_OBJ_EPS) {                       \
+      if (f32) K(float, DV_OBJ_EPS, true); else K(bf16, DV_OBJ_EPS, true);   \
+    } else if (objective == DV_OBJ_X0) {                        \
+      if (f32) K(float, DV_OBJ_X0, true); else K(bf16, DV_OBJ_X0, true);     \
+    } else {                                                    \
+      if (f32) K(float, DV_OBJ_V, true); else K(bf16, DV_OBJ_V, true);       \
+    }                                                           \
+  } while (0)
+
+extern "C" int dv_p_sample_obj(int dtype, const float* x, const void* pred, int ld,
+                               const float* noise, const long long* t, const float* k_x,
+                               const float* k_pred, const float* coef1, const float* coef2,
+                               const float* logvar, const float* dyn_s, float* out, float* x0_out,
+                               int B, int C, int T, int H, int W, int clip, int objective,
+                               int num_timesteps, void* stream) {
+  DV_REQUIRE(x && pred && noise && t && out && num_timesteps > 0, "bad arguments");
+  DV_REQUIRE(objective_ok(objective), "objective is DV_OBJ_EPS, DV_OBJ_X0 or DV_OBJ_V");
+  DV_REQUIRE(objective == DV_OBJ_X0 || (k_x && k_pred), "the eps and v objectives need both x0 tables");
+  DV_REQUIRE(!dyn_s || clip, "a dynamic threshold applies only with clip != 0");
+  const long long n = (long long)B * C * T * H * W;
+  hipStream_t st = (hipStream_t)stream;
+#define DV_PS(TT, OBJ, DYN) p_sample_kernel<TT, OBJ, DYN><<<grid_for(n), 256, 0, st>>>(                   \
+    x, (const TT*)pred, ld, noise, t, k_x, k_pred, coef1, coef2, logvar, dyn_s, out, x0_out, B, C, T, H * W, \
+    clip, num_timesteps)
+  DV_UPDATE_DISPATCH(DV_PS);
+#undef DV_PS
+  return check_launch("p_sample");
+}
+
 extern "C" int dv_p_sample(int dtype, const float* x, const void* eps, int ld, const float* noise,
                            const long long* t, const float* sqrt_recip_ac,
                            const float* sqrt_recipm1_ac, const float* coef1, const float* coef2,
@@ -984,9 +1345,29 @@ extern "C" int dv_p_sample(int dtype, const float* x, const void* eps, int ld, c
   const long long n = (long long)B * C * T * H * W;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH(dtype,
-           (p_sample_kernel<float><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, logvar, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
-           (p_sample_kernel<bf16><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, logvar, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
+           (p_sample_kernel<float, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, logvar, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
+           (p_sample_kernel<bf16, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, sqrt_recip_ac, sqrt_recipm1_ac, coef1, coef2, logvar, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
   return check_launch("p_sample");
+}
+
+extern "C" int dv_ddim_step_obj(int dtype, const float* x, const void* pred, int ld,
+                                const float* noise, const long long* t, const long long* t_next,
+                                const float* alphas_cumprod, float eta, const float* dyn_s,
+                                float* out, float* x0_out, int B, int C, int T, int H, int W,
+                                int clip, int objective, int num_timesteps, void* stream) {
+  DV_REQUIRE(x && pred && t && t_next && alphas_cumprod && out && num_timesteps > 0, "bad arguments");
+  DV_REQUIRE(noise || eta == 0.f, "noise may be NULL only when eta == 0");
+  DV_REQUIRE(ld == 0 ? dtype == DV_F32 : ld >= C, "pred is NCTHW f32 (ld == 0) or channels-last with ld >= C");
+  DV_REQUIRE(objective_ok(objective), "objective is DV_OBJ_EPS, DV_OBJ_X0 or DV_OBJ_V");
+  DV_REQUIRE(!dyn_s || clip, "a dynamic threshold applies only with clip != 0");
+  const long long n = (long long)B * C * T * H * W;
+  hipStream_t st = (hipStream_t)stream;
+#define DV_DD(TT, OBJ, DYN) ddim_step_kernel<TT, OBJ, DYN><<<grid_for(n), 256, 0, st>>>(              \
+    x, (const TT*)pred, ld, noise, t, t_next, alphas_cumprod, eta, dyn_s, out, x0_out, B, C, T, H * W, \
+    clip, num_timesteps)
+  DV_UPDATE_DISPATCH(DV_DD);
+#undef DV_DD
+  return check_launch("ddim_step");
 }
 
 extern "C" int dv_ddim_step(int dtype, const float* x, const void* eps, int ld, const float* noise,
@@ -1000,9 +1381,37 @@ extern "C" int dv_ddim_step(int dtype, const float* x, const void* eps, int ld, 
   const long long n = (long long)B * C * T * H * W;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH(dtype,
-           (ddim_step_kernel<float><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, t_next, alphas_cumprod, eta, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
-           (ddim_step_kernel<bf16><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, t_next, alphas_cumprod, eta, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
+           (ddim_step_kernel<float, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, t_next, alphas_cumprod, eta, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
+           (ddim_step_kernel<bf16, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, t_next, alphas_cumprod, eta, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
   return check_launch("ddim_step");
+}
+
+extern "C" int dv_dyn_thres(int dtype, const float* x, const void* pred, int ld, const long long* t,
+                            const float* k_x, const float* k_pred, int B, int C, int T, int H, int W,
+                            int objective, int num_timesteps, long long k0, float frac, float* s,
+                            void* stream) {
+  DV_REQUIRE(x && pred && t && s && num_timesteps > 0 && B > 0 && C > 0 && T > 0 && H > 0 && W > 0,
+             "bad arguments");
+  DV_REQUIRE(ld == 0 ? dtype == DV_F32 : ld >= C, "pred is NCTHW f32 (ld == 0) or channels-last with ld >= C");
+  DV_REQUIRE(dtype == DV_F32 || dtype == DV_BF16, "unknown dtype");
+  DV_REQUIRE(objective_ok(objective), "objective is DV_OBJ_EPS, DV_OBJ_X0 or DV_OBJ_V");
+  DV_REQUIRE(objective == DV_OBJ_X0 || k_x, "the eps and v objectives need k_x (with k_pred == NULL: alphas_cumprod)");
+  const long long N = (long long)C * T * H * W;
+  DV_REQUIRE(N < (1ll << 31), "more than 2^31 - 1 elements per sample");
+  DV_REQUIRE(k0 >= 0 && k0 < N && frac >= 0.f && frac < 1.f && (frac == 0.f || k0 + 1 < N),
+             "the quantile position k0 + frac lies outside [0, N - 1]");
+  hipStream_t st = (hipStream_t)stream;
+#define DV_DT(TT, OBJ) dyn_thres_kernel<TT, OBJ><<<B, DT_THREADS, 0, st>>>(                     \
+    x, (const TT*)pred, ld, t, k_x, k_pred, C, T * H, W, num_timesteps, k0, frac, s)
+#define DV_DT_T(OBJ)                      \
+  if (dtype == DV_F32) DV_DT(float, OBJ); \
+  else DV_DT(bf16, OBJ)
+  if (objective == DV_OBJ_EPS) { DV_DT_T(DV_OBJ_EPS); }
+  else if (objective == DV_OBJ_X0) { DV_DT_T(DV_OBJ_X0); }
+  else { DV_DT_T(DV_OBJ_V); }
+#undef DV_DT_T
+#undef DV_DT
+  return check_launch("dyn_thres");
 }
 
 extern "C" int dv_resize_nearest(const float* x, float* y, long long planes, int hin, int win,

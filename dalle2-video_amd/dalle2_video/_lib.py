@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("DV_HIP_LIB", os.path.join(_HERE, "libdv_hip.so"))
 
 DV_F32, DV_BF16 = 0, 1
 ACT_NONE, ACT_SILU = 0, 1
+OBJ_EPS, OBJ_X0, OBJ_V = 0, 1, 2  # DV_OBJ_*: what the denoising network predicts
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -81,6 +82,13 @@ _SIGS = {
     "dv_grad_clip_coef": [_P, _L, _F, _F, _P, _P],
     "dv_p_sample": [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "dv_ddim_step": [_I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "dv_diffusion_loss": [_I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "dv_diffusion_loss_bwd": [_I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I,
+                              _P],
+    "dv_p_sample_obj": [_I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I,
+                        _I, _P],
+    "dv_ddim_step_obj": [_I, _P, _P, _I, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "dv_dyn_thres": [_I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _F, _P, _P],
     "dv_xattn_fold": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     "dv_xattn_fwd": [_I, _P, _I, _P, _I, _L, _L, _I, _P, _P, _P, _P, _F, _P, _P, _P],
     "dv_xattn_bwd_tokens": [_I, _P, _I, _P, _I, _P, _I, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],

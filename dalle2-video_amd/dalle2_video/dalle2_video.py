@@ -920,29 +920,48 @@ class _DenoiseStepGraph:
 
     ddim_eta=None is that DDPM step.  A float makes the update the DDIM step
     t -> t_next (ops.ddim_step; the loop at :1811-1876) with a second device
-    buffer `t_next`; at eta == 0 the step draws no noise."""
+    buffer `t_next`; at eta == 0 the step draws no noise.
+
+    objective ("eps", "x0", "v") is what the unet predicts; it selects the
+    update kernel's instantiation and adds no launch.  dyn_percentile (a
+    float: dynamic thresholding, only with clip_denoised) adds the quantile
+    kernel between the noise draw and the update; its output is a fixed
+    device buffer.  The eps step with the static clamp issues exactly the
+    launches and draws it issued before either option existed."""
 
     EAGER_CALLS = 2
 
     def __init__(self, decoder, unet, x, video_embed, noise_scheduler, cond_scale, lowres_cond_vid,
-                 clip_denoised, ddim_eta=None):
+                 clip_denoised, ddim_eta=None, objective="eps", dyn_percentile=None):
         self.decoder, self.unet, self.x = decoder, unet, x
         self.video_embed, self.sched, self.cond_scale = video_embed, noise_scheduler, cond_scale
         self.lowres, self.clip = lowres_cond_vid, clip_denoised
         self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
         self.ddim_eta = ddim_eta
         self.t_next = torch.zeros_like(self.t) if exists(ddim_eta) else None
+        self.objective = objective
+        self.dyn_percentile = dyn_percentile if clip_denoised else None
+        self.dyn_s = (torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+                      if exists(self.dyn_percentile) else None)
         self.calls = 0
         self.graph = None
 
+    def _dyn_scale(self, pred, ddim):
+        if not exists(self.dyn_percentile):
+            return None
+        return ops.dynamic_threshold_scale(self.x, pred, self.t, self.sched, self.objective,
+                                           self.dyn_percentile, ddim=ddim, out=self.dyn_s)
+
     def _ddpm_update(self, eps):
         noise = torch.randn_like(self.x)
-        ops.p_sample_step(self.x, eps, noise, self.t, self.sched, self.clip, out=self.x, want_x0=False)
+        ops.p_sample_step(self.x, eps, noise, self.t, self.sched, self.clip, out=self.x, want_x0=False,
+                          objective=self.objective, dyn_scale=self._dyn_scale(eps, False))
 
     def _ddim_update(self, eps):
         noise = torch.randn_like(self.x) if self.ddim_eta != 0 else None
         ops.ddim_step(self.x, eps, noise, self.t, self.t_next, self.sched, self.ddim_eta, self.clip,
-                      out=self.x, want_x0=False)
+                      out=self.x, want_x0=False, objective=self.objective,
+                      dyn_scale=self._dyn_scale(eps, True))
 
     def _body(self):
         x, unet = self.x, self.unet
@@ -1136,8 +1155,12 @@ class VideoDecoder(nn.Module):
         self.predict_x_start = (cast_tuple(predict_x_start, num_unets)
                                 if not predict_x_start_for_latent_diffusion else (False,) * num_unets)
         self.predict_v = cast_tuple(predict_v, num_unets)
-        if any(self.predict_x_start) or any(self.predict_v):
-            raise NotImplementedError("x0 / v prediction is outside the MI355X hot path")
+        assert len(self.predict_x_start) == num_unets and len(self.predict_v) == num_unets, \
+            "predict_x_start / predict_v take one flag, or one per unet"
+        for ind, (px, pv) in enumerate(zip(self.predict_x_start, self.predict_v)):
+            if px and pv:
+                raise ValueError(f"unet {ind + 1}: predict_x_start and predict_v are both set; "
+                                 "a unet predicts the noise, x0 or v")
         self.input_video_range = (-1.0 if not auto_normalize_video else 0.0, 1.0)
         lowres_conditions = tuple(u.lowres_cond for u in self.unets)
         assert lowres_conditions == (False, *((True,) * (num_unets - 1)))
@@ -1158,8 +1181,9 @@ class VideoDecoder(nn.Module):
         self.can_classifier_guidance = video_cond_drop_prob > 0.0 or text_cond_drop_prob > 0.0
         self.clip_denoised = clip_denoised
         self.clip_x_start = clip_x_start
-        if use_dynamic_thres:
-            raise NotImplementedError("dynamic thresholding is outside the MI355X hot path")
+        # dynamic thresholding (dalle2_video.py:1531-1549): the per-sample
+        # quantile is a device-side select (ops.dynamic_threshold_scale)
+        assert 0.0 <= dynamic_thres_percentile <= 1.0
         self.use_dynamic_thres = use_dynamic_thres
         self.dynamic_thres_percentile = dynamic_thres_percentile
         self.register_buffer("_dummy", torch.Tensor([True]), persistent=False)
@@ -1222,7 +1246,13 @@ class VideoDecoder(nn.Module):
         sw = None
         if noise_scheduler.has_p2_loss_reweighting:
             sw = noise_scheduler.p2_loss_weight.gather(-1, times)
-        return ops.mse_loss_cl(pred, noise, sw)
+        if not (predict_x_start or predict_v):
+            return ops.mse_loss_cl(pred, noise, sw)
+        # x0 / v target (:1988-1995) formed inside the loss kernel from the same
+        # normalised x_start the q_sample kernel noised
+        return ops.diffusion_loss_cl(pred, x_start, noise, times, noise_scheduler,
+                                     ops.objective_name(predict_x_start, predict_v),
+                                     normalize=not is_latent_diffusion, sample_w=sw)
 
     def forward(self, video, video_embed=None, text=None, text_encodings=None, unet_number=None,
                 return_lowres_cond_video=False):
@@ -1249,6 +1279,8 @@ class VideoDecoder(nn.Module):
         video = resize_video_to(video, target_frame_size)
         loss = self.p_losses(unet, video, times, video_embed=video_embed,
                              lowres_cond_video=lowres_cond_video,
+                             predict_x_start=self.predict_x_start[ui],
+                             predict_v=self.predict_v[ui],
                              noise_scheduler=noise_scheduler)
         if not return_lowres_cond_video:
             return loss
@@ -1265,8 +1297,23 @@ class VideoDecoder(nn.Module):
                                             cond_scale=cond_scale,
                                             lowres_cond_video=lowres_cond_vid)
         noise = default(noise, lambda: torch.randn_like(x))
-        out, x0 = ops.p_sample_step(x, pred, noise, t, noise_scheduler, clip_denoised)
+        objective = ops.objective_name(predict_x_start, predict_v)
+        out, x0 = ops.p_sample_step(x, pred, noise, t, noise_scheduler, clip_denoised, objective=objective,
+                                    dyn_scale=self._dyn_scale(x, pred, t, noise_scheduler, objective,
+                                                              clip_denoised, ddim=False))
         return out, x0
+
+    def _dyn_scale(self, x, pred, t, noise_scheduler, objective, clip_denoised, ddim):
+        """The per-sample threshold of dynamic_threshold (:1531-1549), or None
+        for the static clamp; as in the reference it applies only with
+        clip_denoised."""
+        if not (self.use_dynamic_thres and clip_denoised):
+            return None
+        return ops.dynamic_threshold_scale(x, pred, t, noise_scheduler, objective,
+                                           self.dynamic_thres_percentile, ddim=ddim)
+
+    def _dyn_percentile(self):
+        return self.dynamic_thres_percentile if self.use_dynamic_thres else None
 
     @torch.no_grad()
     def p_sample_loop_ddpm(self, unet, shape, video_embed, noise_scheduler, predict_x_start=False,
@@ -1284,7 +1331,9 @@ class VideoDecoder(nn.Module):
         if vid.is_cuda and self.sample_graphs:
             with ops.private_pack_cache():
                 step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
-                                         lowres_cond_vid, clip_denoised)
+                                         lowres_cond_vid, clip_denoised,
+                                         objective=ops.objective_name(predict_x_start, predict_v),
+                                         dyn_percentile=self._dyn_percentile())
                 for time in reversed(range(0, noise_scheduler.num_timesteps)):
                     step(time)
                 del step
@@ -1296,12 +1345,14 @@ class VideoDecoder(nn.Module):
                 times = torch.full((b,), time, device=self.device, dtype=torch.long)
                 vid, _ = self.p_sample(unet, vid, times, video_embed=video_embed,
                                        cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
+                                       predict_x_start=predict_x_start, predict_v=predict_v,
                                        noise_scheduler=noise_scheduler, clip_denoised=clip_denoised)
         return self.unnormalize_video(vid)
 
     @torch.no_grad()
     def p_sample_ddim(self, unet, x, t, t_next, video_embed, noise_scheduler, eta, cond_scale=1.0,
-                      lowres_cond_vid=None, clip_denoised=True, noise=None):
+                      lowres_cond_vid=None, clip_denoised=True, noise=None, predict_x_start=False,
+                      predict_v=False):
         """One DDIM step t -> t_next (the body of the loop at
         dalle2_video.py:1811-1876): returns (x_next, x0).  At eta == 0 no noise
         is drawn."""
@@ -1311,7 +1362,11 @@ class VideoDecoder(nn.Module):
                                             lowres_cond_video=lowres_cond_vid)
         if eta != 0:
             noise = default(noise, lambda: torch.randn_like(x))
-        return ops.ddim_step(x, pred, noise, t, t_next, noise_scheduler, eta, clip_denoised)
+        objective = ops.objective_name(predict_x_start, predict_v)
+        return ops.ddim_step(x, pred, noise, t, t_next, noise_scheduler, eta, clip_denoised,
+                             objective=objective,
+                             dyn_scale=self._dyn_scale(x, pred, t, noise_scheduler, objective,
+                                                       clip_denoised, ddim=True))
 
     @torch.no_grad()
     def p_sample_loop_ddim(self, unet, shape, video_embed, noise_scheduler, timesteps, eta=1.0,
@@ -1341,7 +1396,9 @@ class VideoDecoder(nn.Module):
         if vid.is_cuda and self.sample_graphs:
             with ops.private_pack_cache():
                 step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
-                                         lowres_cond_vid, clip_denoised, ddim_eta=eta)
+                                         lowres_cond_vid, clip_denoised, ddim_eta=eta,
+                                         objective=ops.objective_name(predict_x_start, predict_v),
+                                         dyn_percentile=self._dyn_percentile())
                 for time, time_next in pairs:
                     step(time, time_next)
                 del step
@@ -1353,7 +1410,8 @@ class VideoDecoder(nn.Module):
                 vid, _ = self.p_sample_ddim(unet, vid, times, times_next, video_embed=video_embed,
                                             noise_scheduler=noise_scheduler, eta=eta,
                                             cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
-                                            clip_denoised=clip_denoised)
+                                            clip_denoised=clip_denoised,
+                                            predict_x_start=predict_x_start, predict_v=predict_v)
         return self.unnormalize_video(vid)
 
     @torch.no_grad()
@@ -1385,10 +1443,10 @@ class VideoDecoder(nn.Module):
         is_cuda = next(self.parameters()).is_cuda
         cond_scale = cast_tuple(cond_scale, self.num_unets)
         for (unet_number, unet, vae, channel, frame_size, frame_number, noise_scheduler,
-             lowres_cond, sample_timesteps, unet_cond_scale) in zip(
+             lowres_cond, sample_timesteps, unet_cond_scale, predict_x_start, predict_v) in zip(
                 range(1, self.num_unets + 1), self.unets, self.vaes, self.sample_channels,
                 self.frame_sizes, self.frame_numbers, self.noise_schedulers, self.lowres_conds,
-                self.sample_timesteps, cond_scale):
+                self.sample_timesteps, cond_scale, self.predict_x_start, self.predict_v):
             if unet_number < start_at_unet_number:
                 continue
             ctxm = (self.one_unet_in_gpu(unet=unet, cuda=cuda)
@@ -1402,6 +1460,7 @@ class VideoDecoder(nn.Module):
                 vid = self.p_sample_loop(unet, shape, video_embed=video_embed,
                                          cond_scale=unet_cond_scale,
                                          lowres_cond_vid=lowres_cond_vid,
+                                         predict_x_start=predict_x_start, predict_v=predict_v,
                                          noise_scheduler=noise_scheduler,
                                          timesteps=sample_timesteps,
                                          clip_denoised=True)

@@ -2485,11 +2485,158 @@ def mse_loss_cl(pred_cl, target, sample_w=None):
     return MSELossFn.apply(pred_cl, target, sample_w)
 
 
-def p_sample_step(x, eps, noise, times, sched, clip_denoised=True, out=None, want_x0=True):
+OBJECTIVES = {"eps": _lib.OBJ_EPS, "x0": _lib.OBJ_X0, "v": _lib.OBJ_V}
+
+
+def objective_name(predict_x_start=False, predict_v=False):
+    """The objective of a unet from the reference's two flags (p_losses,
+    dalle2_video.py:1990-1995: predict_v is tested first)."""
+    return "v" if predict_v else "x0" if predict_x_start else "eps"
+
+
+def _objective_code(objective):
+    if objective not in OBJECTIVES:
+        raise _lib.DVError(f"objective must be one of {sorted(OBJECTIVES)}, got {objective!r}")
+    return OBJECTIVES[objective]
+
+
+class DiffusionLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred_cl, x_start, noise, times, sqrt_ac, sqrt_1m_ac, sample_w, normalize, obj):
+        require_gpu(pred_cl, x_start, noise, times)
+        x0 = x_start.float().contiguous()
+        nz = noise.float().contiguous()
+        t = times.to(torch.int64).contiguous()
+        B, C, T, H, W = x0.shape
+        if nz.shape != x0.shape or t.numel() != B:
+            raise _lib.DVError("diffusion_loss: noise is shaped like x_start, times holds one entry per sample")
+        loss = torch.empty((), dtype=torch.float32, device=x0.device)
+        sw = None if sample_w is None else sample_w.float().contiguous()
+        call("dv_diffusion_loss", dt(pred_cl), ptr(pred_cl), cl_ld(pred_cl), ptr(x0), ptr(nz), ptr(t),
+             ptr(sqrt_ac), ptr(sqrt_1m_ac), B, C, T, H, W, int(normalize), obj, sqrt_ac.numel(), ptr(sw),
+             ptr(loss), stream())
+        ctx.save_for_backward(pred_cl, x0, nz, t, sqrt_ac, sqrt_1m_ac, sw)
+        ctx.meta = (int(normalize), obj)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dl):
+        pred_cl, x0, nz, t, sqrt_ac, sqrt_1m_ac, sw = ctx.saved_tensors
+        normalize, obj = ctx.meta
+        B, C, T, H, W = x0.shape
+        dlc = dl.float().contiguous().reshape(1)
+        cp = pred_cl.shape[-1]
+        alloc = torch.zeros if cp != C else torch.empty
+        dp = alloc(pred_cl.shape, dtype=pred_cl.dtype, device=pred_cl.device)
+        call("dv_diffusion_loss_bwd", dt(pred_cl), ptr(pred_cl), cl_ld(pred_cl), ptr(x0), ptr(nz), ptr(t),
+             ptr(sqrt_ac), ptr(sqrt_1m_ac), B, C, T, H, W, normalize, obj, sqrt_ac.numel(), ptr(sw), ptr(dlc),
+             ptr(dp), cp, stream())
+        return dp, None, None, None, None, None, None, None, None
+
+
+def diffusion_loss_cl(pred_cl, x_start, noise, times, sched, objective="eps", normalize=True, sample_w=None):
+    """l2 loss of the channels-last prediction against the objective's target
+    (p_losses, dalle2_video.py:1988-2002), the target formed inside the kernel:
+    eps: noise; x0: xs; v: sqrt(ac[t]) noise - sqrt(1 - ac[t]) xs, with
+    xs = 2 x_start - 1 when `normalize` (what q_sample_cl noised)."""
+    return DiffusionLossFn.apply(pred_cl, x_start, noise, times, sched.sqrt_alphas_cumprod,
+                                 sched.sqrt_one_minus_alphas_cumprod, sample_w, normalize,
+                                 _objective_code(objective))
+
+
+def _pred_layout(name, pred, xf):
+    """(tensor, ld, dtype code) of a network output given as NCTHW f32 or as
+    channels-last frames."""
+    B, C, T, H, W = xf.shape
+    if pred.dim() == 5:
+        pf = pred.float().contiguous()
+        if pf.shape != xf.shape:
+            raise _lib.DVError(f"{name}: pred {tuple(pred.shape)} does not match x {tuple(xf.shape)}")
+        return pf, 0, _lib.DV_F32
+    if pred.shape[0] != B * T or tuple(pred.shape[1:3]) != (H, W) or pred.shape[-1] < C:
+        raise _lib.DVError(f"{name}: pred {tuple(pred.shape)} does not match x {tuple(xf.shape)}")
+    return pred, cl_ld(pred), dt(pred)
+
+
+def _x0_tables(sched, objective):
+    """The gathered factor tables (k_x, k_pred) of x0 = k_x[t] x - k_pred[t] pred."""
+    if objective == "eps":
+        return sched.sqrt_recip_alphas_cumprod, sched.sqrt_recipm1_alphas_cumprod
+    if objective == "v":
+        return sched.sqrt_alphas_cumprod, sched.sqrt_one_minus_alphas_cumprod
+    return None, None
+
+
+def dynamic_threshold_scale(x, pred, times, sched, objective="eps", percentile=0.95, ddim=False, out=None):
+    """s[b] = max(1, quantile(|x0_u[b]|, percentile)) of dynamic_threshold
+    (dalle2_video.py:1531-1549; torch.quantile's linear interpolation), by an
+    exact per-sample radix select on the device.  x0_u is derived from
+    (x, pred, times) as p_sample_step derives it, or with ddim=True as
+    ddim_step does; it is not written anywhere.  Returns B f32 values for the
+    `dyn_scale` argument of those two."""
+    require_gpu(x, pred, times)
+    code = _objective_code(objective)
+    xf = x.float().contiguous()
+    t = times.to(torch.int64).contiguous()
+    B, C, T, H, W = xf.shape
+    if t.numel() != B:
+        raise _lib.DVError("dynamic_threshold_scale: times holds one entry per sample")
+    pf, ld, pdt = _pred_layout("dynamic_threshold_scale", pred, xf)
+    percentile = float(percentile)
+    if not 0.0 <= percentile <= 1.0:
+        raise _lib.DVError("dynamic_threshold_scale: percentile must lie in [0, 1]")
+    pos = percentile * (C * T * H * W - 1)  # float64, as torch.quantile places it
+    k0 = int(pos)
+    frac = pos - k0
+    if frac >= 1.0 - 2.0 ** -25:  # rounds to 1 in f32: the next order statistic itself
+        k0, frac = k0 + 1, 0.0
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=xf.device)
+    kx, kp = (sched.alphas_cumprod, None) if ddim else _x0_tables(sched, objective)
+    call("dv_dyn_thres", pdt, ptr(xf), ptr(pf), ld, ptr(t), ptr(kx), ptr(kp), B, C, T, H, W, code,
+         sched.alphas_cumprod.numel(), k0, ctypes_float(frac), ptr(out), stream())
+    return out
+
+
+def _check_dyn_scale(name, dyn_scale, B, clip_denoised):
+    if dyn_scale is None:
+        return
+    require_gpu(dyn_scale)
+    if dyn_scale.dtype != torch.float32 or not dyn_scale.is_contiguous() or dyn_scale.numel() != B:
+        raise _lib.DVError(f"{name}: dyn_scale holds one contiguous f32 value per sample")
+    if not clip_denoised:
+        raise _lib.DVError(f"{name}: dyn_scale applies only with clip_denoised")
+
+
+def p_sample_step(x, eps, noise, times, sched, clip_denoised=True, out=None, want_x0=True, objective="eps",
+                  dyn_scale=None):
     """x0 = sqrt(1/ac) x - sqrt(1/ac - 1) eps -> clamp -> posterior mean + sigma z
     (p_mean_variance + p_sample, dalle2_video.py:1551-1664).  eps is an NCTHW
     f32 tensor or a channels-last frame tensor.  `out` may be x itself (the
-    update is elementwise: the sampling loop advances its state in place)."""
+    update is elementwise: the sampling loop advances its state in place).
+    objective "x0" / "v": `eps` is that prediction and x0 is derived from it
+    (:1589-1595).  dyn_scale (dynamic_threshold_scale) replaces the clamp at 1
+    by clamp(x0, -s, s)/s."""
+    code = _objective_code(objective)
+    if code != _lib.OBJ_EPS or dyn_scale is not None:
+        require_gpu(x, eps, noise, times)
+        xf = x.float().contiguous()
+        nz = noise.float().contiguous()
+        t = times.to(torch.int64).contiguous()
+        B, C, T, H, W = xf.shape
+        ef, ld, edt = _pred_layout("p_sample", eps, xf)
+        _check_dyn_scale("p_sample", dyn_scale, B, clip_denoised)
+        if out is None:
+            out = torch.empty_like(xf)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != xf.shape:
+            raise _lib.DVError("p_sample: out must be a contiguous f32 tensor shaped like x")
+        x0 = torch.empty_like(xf) if want_x0 else None
+        kx, kp = _x0_tables(sched, objective)
+        call("dv_p_sample_obj", edt, ptr(xf), ptr(ef), ld, ptr(nz), ptr(t), ptr(kx), ptr(kp),
+             ptr(sched.posterior_mean_coef1), ptr(sched.posterior_mean_coef2),
+             ptr(sched.posterior_log_variance_clipped), ptr(dyn_scale), ptr(out), ptr(x0), B, C, T, H, W,
+             int(clip_denoised), code, sched.sqrt_recip_alphas_cumprod.numel(), stream())
+        return out, x0
     require_gpu(x, eps, noise, times)
     xf = x.float().contiguous()
     nz = noise.float().contiguous()
@@ -2515,14 +2662,17 @@ def p_sample_step(x, eps, noise, times, sched, clip_denoised=True, out=None, wan
     return out, x0
 
 
-def ddim_step(x, eps, noise, times, times_next, sched, eta, clip_denoised=True, out=None, want_x0=True):
+def ddim_step(x, eps, noise, times, times_next, sched, eta, clip_denoised=True, out=None, want_x0=True,
+              objective="eps", dyn_scale=None):
     """One DDIM step times -> times_next (p_sample_loop_ddim,
     dalle2_video.py:1811-1876): x0 as in p_sample_step, then
     x0 sqrt(ac[t_next]) + c1 z + c2 pred_noise with c1 = eta sqrt((1 - a/an)
     (1 - an)/(1 - a)), c2 = sqrt((1 - an) - c1^2).  The kernel derives every
     coefficient from sched.alphas_cumprod.  eps and `out` as p_sample_step;
-    noise may be None when eta == 0 (c1 = 0: the draw would be dead)."""
+    noise may be None when eta == 0 (c1 = 0: the draw would be dead).
+    objective / dyn_scale as p_sample_step (:1847-1867)."""
     require_gpu(x, eps, noise, times, times_next)
+    code = _objective_code(objective)
     eta = float(eta)
     if noise is None and eta != 0.0:
         raise _lib.DVError("ddim_step: noise may be None only when eta == 0")
@@ -2548,6 +2698,12 @@ def ddim_step(x, eps, noise, times, times_next, sched, eta, clip_denoised=True, 
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != xf.shape:
         raise _lib.DVError("ddim_step: out must be a contiguous f32 tensor shaped like x")
     x0 = torch.empty_like(xf) if want_x0 else None
+    if code != _lib.OBJ_EPS or dyn_scale is not None:
+        _check_dyn_scale("ddim_step", dyn_scale, B, clip_denoised)
+        call("dv_ddim_step_obj", edt, ptr(xf), ptr(ef), ld, ptr(nz), ptr(t), ptr(tn), ptr(sched.alphas_cumprod),
+             ctypes_float(eta), ptr(dyn_scale), ptr(out), ptr(x0), B, C, T, H, W, int(clip_denoised), code,
+             sched.alphas_cumprod.numel(), stream())
+        return out, x0
     call("dv_ddim_step", edt, ptr(xf), ptr(ef), ld, ptr(nz), ptr(t), ptr(tn), ptr(sched.alphas_cumprod),
          ctypes_float(eta), ptr(out), ptr(x0), B, C, T, H, W, int(clip_denoised),
          sched.alphas_cumprod.numel(), stream())

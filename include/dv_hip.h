@@ -31,6 +31,9 @@ extern "C" {
 enum { DV_F32 = 0, DV_BF16 = 1 };
 enum { DV_OK = 0, DV_ERR_INVALID = -1, DV_ERR_LAUNCH = -2, DV_ERR_UNSUPPORTED = -3 };
 enum { DV_ACT_NONE = 0, DV_ACT_SILU = 1, DV_ACT_GELU = 2 };
+/* what the denoising network predicts (VideoDecoder predict_x_start /
+ * predict_v): the noise, x0, or v = sqrt(a) noise - sqrt(1 - a) x0           */
+enum { DV_OBJ_EPS = 0, DV_OBJ_X0 = 1, DV_OBJ_V = 2 };
 
 const char* dv_last_error(void);
 int dv_abi_version(void);
@@ -445,6 +448,61 @@ int dv_ddim_step(int dtype, const float* x, const void* eps, int ld, const float
                  const long long* t, const long long* t_next, const float* alphas_cumprod,
                  float eta, float* out, float* x0_out, int B, int C, int T, int H, int W,
                  int clip, int num_timesteps, void* stream);
+
+/* ---- x0 / v objectives and dynamic thresholding (ABI 6) -------------------
+ * Below a = alphas_cumprod[t]; `objective` is a DV_OBJ_* code.
+ *
+ * dv_diffusion_loss: the l2 loss of p_losses (:1988-2002) against the target
+ * of the objective, formed per element from the NCTHW f32 x_start and noise
+ * (no target tensor is written):
+ *   eps: noise      x0: xs      v: sqrt_ac[t] noise - sqrt_1m_ac[t] xs
+ * with xs = 2 x_start - 1 when normalize != 0 (as dv_q_sample), else x_start.
+ * pred / ld / sample_w / loss / dpred / lddp as dv_mse_loss(_bwd); DV_OBJ_EPS
+ * runs dv_mse_loss(_bwd) on `noise`.  For x0 and v a t outside
+ * [0, num_timesteps) makes the loss (and that sample's gradient) NaN.        */
+int dv_diffusion_loss(int dtype, const void* pred, int ld, const float* x_start, const float* noise,
+                      const long long* t, const float* sqrt_ac, const float* sqrt_1m_ac, int B,
+                      int C, int T, int H, int W, int normalize, int objective, int num_timesteps,
+                      const float* sample_w, float* loss, void* stream);
+int dv_diffusion_loss_bwd(int dtype, const void* pred, int ld, const float* x_start,
+                          const float* noise, const long long* t, const float* sqrt_ac,
+                          const float* sqrt_1m_ac, int B, int C, int T, int H, int W, int normalize,
+                          int objective, int num_timesteps, const float* sample_w,
+                          const float* dloss, void* dpred, int lddp, void* stream);
+/* dv_p_sample / dv_ddim_step for any objective (p_mean_variance :1585-1598,
+ * the DDIM loop :1843-1867).  The unthresholded x0 is
+ *   eps: sqrt(1/a) x - sqrt(1/a - 1) pred    x0: pred
+ *   v  : sqrt(a) x - sqrt(1 - a) pred
+ * dv_p_sample_obj gathers the two factors from k_x / k_pred
+ * (eps: sqrt_recip_ac, sqrt_recipm1_ac; v: sqrt_ac, sqrt_1m_ac; x0: unused,
+ * may be NULL); dv_ddim_step_obj derives them from alphas_cumprod like its
+ * other coefficients, and forms pred_noise without cancellation.
+ * With clip != 0 x0 is clamped to [-1, 1], or, when dyn_s (B floats written
+ * by dv_dyn_thres) is given, to [-s, s] and divided by s.  DV_OBJ_EPS with
+ * dyn_s == NULL launches the kernel of dv_p_sample / dv_ddim_step.           */
+int dv_p_sample_obj(int dtype, const float* x, const void* pred, int ld, const float* noise,
+                    const long long* t, const float* k_x, const float* k_pred, const float* coef1,
+                    const float* coef2, const float* logvar, const float* dyn_s, float* out,
+                    float* x0_out, int B, int C, int T, int H, int W, int clip, int objective,
+                    int num_timesteps, void* stream);
+int dv_ddim_step_obj(int dtype, const float* x, const void* pred, int ld, const float* noise,
+                     const long long* t, const long long* t_next, const float* alphas_cumprod,
+                     float eta, const float* dyn_s, float* out, float* x0_out, int B, int C, int T,
+                     int H, int W, int clip, int objective, int num_timesteps, void* stream);
+/* the threshold of dynamic_threshold (:1531-1549), per sample:
+ *   s[b] = max(1, quantile(|x0_u[b]| over C*T*H*W, p))
+ * with torch.quantile's linear interpolation.  The caller splits the position
+ * p (N - 1), N = C*T*H*W, into k0 = floor and frac in [0, 1); the kernel
+ * selects the order statistics k0 and k0 + 1 exactly and writes
+ * v[k0] + frac (v[k0+1] - v[k0]).  x0_u is recomputed from x, pred and t as in
+ * the update kernels (k_pred != NULL: the tables of dv_p_sample_obj;
+ * k_pred == NULL: k_x is alphas_cumprod, the form of dv_ddim_step_obj) and is
+ * never written.  One workgroup per sample, no workspace, no host sync.  A
+ * sample with t outside the schedule or a non-finite x0_u gets s = NaN.       */
+int dv_dyn_thres(int dtype, const float* x, const void* pred, int ld, const long long* t,
+                 const float* k_x, const float* k_pred, int B, int C, int T, int H, int W,
+                 int objective, int num_timesteps, long long k0, float frac, float* s,
+                 void* stream);
 
 /* ---- time conditioning MLPs (Unet3D.to_time_hiddens / to_time_tokens /
  * to_time_cond, dalle2_video.py:348-357; ResnetBlock3D.time_mlp, :152-155)
