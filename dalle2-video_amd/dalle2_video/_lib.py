@@ -38,6 +38,8 @@ _SIGS = {
     "dv_conv_fwd_mx8": [_P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     "dv_xattn_fold_batched": [_I, _P, _I, _F, _P],
     "dv_xattn_fold_bwd_batched": [_P, _I, _F, _P],
+    "dv_xattn_fold_batched_nk": [_I, _P, _I, _I, _F, _P],
+    "dv_xattn_fold_bwd_batched_nk": [_P, _I, _I, _F, _P],
     "dv_conv_wgrad_ws": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "dv_conv_wgrad": [_I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "dv_conv_wgrad_deferred": [_I, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _L, _I, _I, _I, _I, _I, _I,
@@ -93,6 +95,10 @@ _SIGS = {
     "dv_xattn_fwd": [_I, _P, _I, _P, _I, _L, _L, _I, _P, _P, _P, _P, _F, _P, _P, _P],
     "dv_xattn_bwd_tokens": [_I, _P, _I, _P, _I, _P, _I, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "dv_xattn_fold_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P],
+    "dv_xattn_fold_nk": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "dv_xattn_fwd_nk": [_I, _P, _I, _P, _I, _L, _L, _I, _I, _P, _P, _P, _P, _F, _P, _P, _P],
+    "dv_xattn_bwd_tokens_nk": [_I, _P, _I, _P, _I, _P, _I, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "dv_xattn_fold_bwd_nk": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _I, _P],
     "dv_gemm_tn_batched": [_I, _P, _I, _P, _I, _P, _L, _I, _I, _I, _P],
     "dv_gemm_tn_batched_multi": [_I, _I, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P],
     "dv_resize_nearest": [_P, _P, _L, _I, _I, _I, _I, _I, _F, _F, _P],

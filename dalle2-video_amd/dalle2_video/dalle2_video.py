@@ -566,7 +566,6 @@ class Unet3D(nn.Module):
                            cross_embed_downsample=cross_embed_downsample,
                            combine_upsample_fmaps=combine_upsample_fmaps,
                            cond_on_text_encodings=cond_on_text_encodings, self_cond=self_cond,
-                           cond_on_video_embeds=cond_on_video_embeds,
                            lowres_noise_cond=lowres_noise_cond,
                            scale_skip_connection=scale_skip_connection,
                            cosine_sim_self_attn=cosine_sim_self_attn,
@@ -594,8 +593,27 @@ class Unet3D(nn.Module):
         self.to_time_tokens = nn.Sequential(nn.Linear(tcd, cond_dim * num_time_tokens),
                                             Rearrange("b (r d) -> b r d", r=num_time_tokens))
         self.to_time_cond = nn.Sequential(nn.Linear(tcd, tcd))
-        self.video_to_tokens = nn.Identity()
-        self.to_video_hiddens = None
+        # dalle2_video.py:359-372: the video embedding becomes num_image_tokens
+        # context tokens next to the time tokens, and (optionally) a term of t
+        if cond_on_video_embeds:
+            if not exists(video_embed_dim):
+                raise ValueError("cond_on_video_embeds=True needs video_embed_dim")
+            if video_embed_dim == cond_dim or num_image_tokens != 4 or num_time_tokens != 2:
+                # the cross-attention kernels run 3 or 7 keys per head; the reference's
+                # Identity case (video_embed_dim == cond_dim) is a single video token
+                raise NotImplementedError(
+                    "Unet3D(cond_on_video_embeds=True) on MI355X runs 2 time tokens + 4 video "
+                    "tokens projected from video_embed_dim != cond_dim")
+            self.video_to_tokens = nn.Sequential(
+                nn.Linear(video_embed_dim, cond_dim * num_image_tokens),
+                Rearrange("b (n d) -> b n d", n=num_image_tokens))
+            self.to_video_hiddens = nn.Sequential(nn.Linear(video_embed_dim, tcd), nn.GELU()) \
+                if add_video_embeds_to_time else None
+        else:
+            self.video_to_tokens = nn.Identity()
+            self.to_video_hiddens = None
+        self.video_embed_dim = video_embed_dim
+        self.num_image_tokens = num_image_tokens
         self.norm_cond = nn.LayerNorm(cond_dim)
         self.norm_mid_cond = nn.LayerNorm(cond_dim)
         self.text_to_cond = None
@@ -666,8 +684,9 @@ class Unet3D(nn.Module):
         # off: measured slower than the bf16 kernel on MI355X
         self.fp8_attention = False
 
-    # dalle2_video.py:652-681 — `cond_on_image_embeds` is swallowed by **kwargs
-    # so the rebuilt unet keeps cond_on_video_embeds=False.
+    # dalle2_video.py:652-681 — `cond_on_image_embeds` is swallowed by **kwargs,
+    # so the rebuilt unet keeps the cond_on_video_embeds its user set, which
+    # lives in _locals: False stays False, True stays True.
     def cast_model_parameters(self, *, lowres_cond, lowres_noise_cond, channels, channels_out,
                               cond_on_image_embeds, cond_on_text_encodings):
         if (lowres_cond == self.lowres_cond and channels == self.channels
@@ -693,21 +712,43 @@ class Unet3D(nn.Module):
         return null + (logits - null) * cond_scale
 
     # ---- conditioning ----------------------------------------------------
-    def _conditioning(self, time, batch, device, video_cond_drop_prob, text_cond_drop_prob):
+    def _conditioning(self, time, batch, device, video_cond_drop_prob, text_cond_drop_prob,
+                      video_embed=None):
         th = ops.linear_small(ops.sinusoidal(time, self.dim), self.to_time_hiddens[1].weight,
                               self.to_time_hiddens[1].bias, act_out=ops.ACT_OUT_GELU)
         tt = ops.linear_small(th, self.to_time_tokens[0].weight, self.to_time_tokens[0].bias)
         t = ops.linear_small(th, self.to_time_cond[0].weight, self.to_time_cond[0].bias)
-        # dalle2_video.py:772-779: two keep-masks drawn from the device RNG; at this
-        # configuration their values are dead (no video/text tokens), but the draws stay
-        prob_mask_like((batch,), 1 - video_cond_drop_prob, device=device)
+        # dalle2_video.py:772-779: two keep-masks drawn from the device RNG; without
+        # video conditioning the first is dead, and the text one always is, but the
+        # draws stay
+        video_keep_mask = prob_mask_like((batch,), 1 - video_cond_drop_prob, device=device)
         prob_mask_like((batch,), 1 - text_cond_drop_prob, device=device)
+        ntok = self.num_time_tokens
+        if self.cond_on_video_embeds:
+            # dalle2_video.py:784-809, 852-855: dropped samples take the learned null
+            # hiddens / tokens; the selects stay on the device (no host sync)
+            if not exists(video_embed):
+                raise ValueError("this Unet3D was built with cond_on_video_embeds=True: "
+                                 "video_embed is required")
+            if video_embed.dim() != 2 or video_embed.shape != (batch, self.video_embed_dim):
+                raise ValueError(f"video_embed must be ({batch}, {self.video_embed_dim}), got "
+                                 f"{tuple(video_embed.shape)}")
+            ve = video_embed.float()
+            if exists(self.to_video_hiddens):
+                vh = ops.linear_small(ve, self.to_video_hiddens[0].weight,
+                                      self.to_video_hiddens[0].bias, act_out=ops.ACT_OUT_GELU)
+                t = t + torch.where(video_keep_mask[:, None], vh, self.null_video_hiddens.float())
+            vtok = ops.linear_small(ve, self.video_to_tokens[0].weight, self.video_to_tokens[0].bias)
+            vtok = torch.where(video_keep_mask[:, None, None],
+                               vtok.reshape(batch, self.num_image_tokens, self.cond_dim),
+                               self.null_video_embed.float())
+            tt = torch.cat((tt.reshape(batch, ntok, self.cond_dim), vtok), dim=1)
+            ntok += self.num_image_tokens
         tt = tt.reshape(-1, self.cond_dim)
         c = ops.layer_norm(tt, self.norm_cond.weight, self.norm_cond.bias,
-                           eps=self.norm_cond.eps).reshape(batch, self.num_time_tokens, self.cond_dim)
+                           eps=self.norm_cond.eps).reshape(batch, ntok, self.cond_dim)
         mid_c = ops.layer_norm(tt, self.norm_mid_cond.weight, self.norm_mid_cond.bias,
-                               eps=self.norm_mid_cond.eps).reshape(batch, self.num_time_tokens,
-                                                                   self.cond_dim)
+                               eps=self.norm_mid_cond.eps).reshape(batch, ntok, self.cond_dim)
         return t, c, mid_c
 
     def _resnet_blocks(self):
@@ -735,7 +776,7 @@ class Unet3D(nn.Module):
             xa = [b for b, m in blks if m == use_mid and exists(b.cross_attn)]
             if not xa:
                 continue
-            kvs = ops.linear_group(ctx.reshape(-1, ctx.shape[-1]),
+            kvs = ops.linear_group_rows(ctx.reshape(-1, ctx.shape[-1]),
                                    [b.cross_attn.to_kv.weight for b in xa], [None] * len(xa))
             for b, kv in zip(xa, kvs):
                 pre.setdefault(id(b), [None, None])[1] = kv
@@ -748,24 +789,26 @@ class Unet3D(nn.Module):
         return {k: (v[0], v[1], folds.get(k)) for k, v in pre.items()}
 
     def forward_cl(self, x, time, *, batch, lowres_cl=None, video_cond_drop_prob=0.0,
-                   text_cond_drop_prob=0.0):
+                   text_cond_drop_prob=0.0, video_embed=None):
         """Core denoiser on channels-last frames x (batch*T, H, W, C8); returns
-        channels-last (batch*T, H, W, channels_out)."""
+        channels-last (batch*T, H, W, channels_out).  video_embed (batch, E): used
+        (and required) by a unet built with cond_on_video_embeds=True."""
         if getattr(self, "fp8", False) and not torch.is_grad_enabled():
             with ops.mx8_convs(attention=getattr(self, "fp8_attention", False)):
                 return self._forward_cl(x, time, batch=batch, lowres_cl=lowres_cl,
                                         video_cond_drop_prob=video_cond_drop_prob,
-                                        text_cond_drop_prob=text_cond_drop_prob)
+                                        text_cond_drop_prob=text_cond_drop_prob,
+                                        video_embed=video_embed)
         return self._forward_cl(x, time, batch=batch, lowres_cl=lowres_cl,
                                 video_cond_drop_prob=video_cond_drop_prob,
-                                text_cond_drop_prob=text_cond_drop_prob)
+                                text_cond_drop_prob=text_cond_drop_prob, video_embed=video_embed)
 
     def _forward_cl(self, x, time, *, batch, lowres_cl=None, video_cond_drop_prob=0.0,
-                    text_cond_drop_prob=0.0):
+                    text_cond_drop_prob=0.0, video_embed=None):
         x = self.init_conv.forward_cl(x)
         r = x
         t, c, mid_c = self._conditioning(time, batch, x.device, video_cond_drop_prob,
-                                         text_cond_drop_prob)
+                                         text_cond_drop_prob, video_embed)
         pre = self._grouped_projections(t, c, mid_c, batch, x.dtype)
 
         mark = ops.backward_mark  # backward progress marks (trainer's overlapped all-reduce)
@@ -827,7 +870,7 @@ class Unet3D(nn.Module):
         lcl = ops.to_cl(lowres_cond_video, dt) if exists(lowres_cond_video) else None
         y = self.forward_cl(xcl, time, batch=batch, lowres_cl=lcl,
                             video_cond_drop_prob=video_cond_drop_prob,
-                            text_cond_drop_prob=text_cond_drop_prob)
+                            text_cond_drop_prob=text_cond_drop_prob, video_embed=video_embed)
         return ops.from_cl(y, batch, self.channels_out, x.shape[2])
 
 
@@ -927,7 +970,10 @@ class _DenoiseStepGraph:
     float: dynamic thresholding, only with clip_denoised) adds the quantile
     kernel between the noise draw and the update; its output is a fixed
     device buffer.  The eps step with the static clamp issues exactly the
-    launches and draws it issued before either option existed."""
+    launches and draws it issued before either option existed.
+
+    For a unet built with cond_on_video_embeds=True, `video_embed` is a third
+    fixed device buffer read by every forward of the step."""
 
     EAGER_CALLS = 2
 
@@ -935,6 +981,10 @@ class _DenoiseStepGraph:
                  clip_denoised, ddim_eta=None, objective="eps", dyn_percentile=None):
         self.decoder, self.unet, self.x = decoder, unet, x
         self.video_embed, self.sched, self.cond_scale = video_embed, noise_scheduler, cond_scale
+        if getattr(unet, "cond_on_video_embeds", False) and exists(video_embed):
+            # a graph input: the captured step reads this fixed f32 buffer, so
+            # copying another embedding into it redirects every later replay
+            self.video_embed = video_embed.detach().float().contiguous().clone()
         self.lowres, self.clip = lowres_cond_vid, clip_denoised
         self.t = torch.zeros(x.shape[0], dtype=torch.long, device=x.device)
         self.ddim_eta = ddim_eta
@@ -971,7 +1021,8 @@ class _DenoiseStepGraph:
             dt = _compute_dtype(unet, x)
             xin = torch.cat((x, self.lowres), dim=1) if exists(self.lowres) else x
             lcl = ops.to_cl(self.lowres, dt) if exists(self.lowres) else None
-            eps = unet.forward_cl(ops.to_cl(xin, dt), self.t, batch=x.shape[0], lowres_cl=lcl)
+            eps = unet.forward_cl(ops.to_cl(xin, dt), self.t, batch=x.shape[0], lowres_cl=lcl,
+                                  video_embed=self.video_embed)
         else:
             eps = unet.forward_with_cond_scale(x, self.t, video_embed=self.video_embed,
                                                cond_scale=self.cond_scale,
@@ -1242,7 +1293,8 @@ class VideoDecoder(nn.Module):
             xn[..., C:C + lc] = lcl[..., :lc]  # the channel concat (dalle2_video.py:744)
         pred = unet.forward_cl(xn, times, batch=B, lowres_cl=lcl,
                                video_cond_drop_prob=self.video_cond_drop_prob,
-                               text_cond_drop_prob=self.text_cond_drop_prob)
+                               text_cond_drop_prob=self.text_cond_drop_prob,
+                               video_embed=video_embed)
         sw = None
         if noise_scheduler.has_p2_loss_reweighting:
             sw = noise_scheduler.p2_loss_weight.gather(-1, times)

@@ -605,21 +605,21 @@ class defer_wgrad:
 _XA_WS = {}
 
 
-def _xattn_workspace(nb, C, device, owner=None):
-    """Cross-attention backward accumulators (wsR, wsV, wsQ [nb][32][C]): zero
-    on entry, re-zeroed by dv_xattn_fold_bwd after use; mcorr [nb][32] scratch.
+def _xattn_workspace(nb, C, device, owner=None, KP=32):
+    """Cross-attention backward accumulators (wsR, wsV, wsQ [nb][KP][C]): zero
+    on entry, re-zeroed by dv_xattn_fold_bwd after use; mcorr [nb][KP] scratch.
     `owner` (a block's parameter) gives the block its own set, for fold
     backwards deferred into one batched launch."""
     import weakref
-    key = (nb, C, str(device), None if owner is None else id(owner))
+    key = (nb, C, str(device), None if owner is None else id(owner)) + ((KP,) if KP != 32 else ())
     ent = _XA_WS.get(key)
     if ent is not None and (owner is None or ent[0]() is owner):
         return ent[1]
     if owner is not None:  # forget the sets of blocks that no longer exist
         for k in [k for k, e in _XA_WS.items() if e[0] is not None and e[0]() is None]:
             del _XA_WS[k]
-    ws = tuple(torch.zeros(nb, 32, C, dtype=torch.float32, device=device) for _ in range(3)) + (
-        torch.zeros(nb, 32, dtype=torch.float32, device=device),)
+    ws = tuple(torch.zeros(nb, KP, C, dtype=torch.float32, device=device) for _ in range(3)) + (
+        torch.zeros(nb, KP, dtype=torch.float32, device=device),)
     _XA_WS[key] = (None if owner is None else weakref.ref(owner), ws)
     return ws
 
@@ -2003,6 +2003,22 @@ def linear_group(x, weights, biases, act_in=0):
     return list(LinearGroupFn.apply(x, act_in, len(weights), *weights, *biases))
 
 
+def linear_group_rows(x, weights, biases, act_in=0):
+    """linear_group over any number of rows: the kernel takes up to 8 rows a
+    launch (2 time tokens x 4 clips); the 6 context tokens per clip of a video-
+    conditioned unet go through it 8 rows at a time.
+
+    Backward ordering: a deferred cross-attention fold backward hands autograd a
+    dkv that flush_fold_bwd() fills later.  The cat below passes each chunk's
+    LinearGroupFn.backward a dim-0 narrow VIEW of that tensor, and that backward
+    calls flush_fold_bwd() before it reads, so the view is filled by then.  Do
+    not put anything that copies the gradient between the cat and the chunks."""
+    if x.shape[0] <= 8 or len(weights) == 0:
+        return linear_group(x, weights, biases, act_in)
+    parts = [linear_group(x[i:i + 8], weights, biases, act_in) for i in range(0, x.shape[0], 8)]
+    return [torch.cat(p, dim=0) for p in zip(*parts)]
+
+
 _FREQS = {}
 
 
@@ -2033,6 +2049,22 @@ def sinusoidal(times: torch.Tensor, dim: int) -> torch.Tensor:
 XA_HEADS, XA_DH = 8, 64
 
 
+def xattn_keys(kv_rows, nb):
+    """Keys per head (the null key + the context tokens per batch element) of a
+    cross-attention call whose to_kv(context) has kv_rows rows; the kernels run
+    3 (time tokens) or 7 (time + video tokens)."""
+    nk = 1 + kv_rows // max(nb, 1)
+    if kv_rows % max(nb, 1) or nk not in (3, 7):
+        raise _lib.DVError(f"cross attention runs 3 or 7 keys per head (2 or 6 context tokens per "
+                           f"batch element), got {kv_rows} kv rows for {nb} batch elements")
+    return nk
+
+
+def _xattn_kp(nk):
+    """Padded key rows of the operand images: one 32-row MFMA tile per 4 keys."""
+    return 32 * ((nk + 1) // 4)
+
+
 class DvFoldBwdJob(ctypes.Structure):
     """struct DvFoldBwdJob of dv_hip.h (dv_xattn_fold_bwd_batched)."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("wsR", "wsV", "wsQ", "mcorr", "at", "vt", "g1", "wq",
@@ -2052,11 +2084,17 @@ def flush_fold_bwd():
     to_kv backward, which consumes their kv gradients, before anything else)."""
     global _FOLD_BWD_PENDING
     pend, _FOLD_BWD_PENDING = _FOLD_BWD_PENDING, []
-    for i in range(0, len(pend), 20):  # DV_FOLD_BWD_MAX
-        part = pend[i:i + 20]
-        jobs = (DvFoldBwdJob * len(part))(*[j for j, _ in part])
-        call("dv_xattn_fold_bwd_batched", ctypes.cast(jobs, ctypes.c_void_p), len(part),
-             ctypes_float(XA_DH ** -0.5), stream())
+    for nk in sorted({e[2] for e in pend}):  # a launch runs one key count
+        same = [e for e in pend if e[2] == nk]
+        for i in range(0, len(same), 20):  # DV_FOLD_BWD_MAX
+            part = same[i:i + 20]
+            jobs = (DvFoldBwdJob * len(part))(*[e[0] for e in part])
+            if nk == 3:
+                call("dv_xattn_fold_bwd_batched", ctypes.cast(jobs, ctypes.c_void_p), len(part),
+                     ctypes_float(XA_DH ** -0.5), stream())
+            else:
+                call("dv_xattn_fold_bwd_batched_nk", ctypes.cast(jobs, ctypes.c_void_p), len(part), nk,
+                     ctypes_float(XA_DH ** -0.5), stream())
 
 
 class DvFoldJob(ctypes.Structure):
@@ -2072,18 +2110,20 @@ class XattnFold:
 
     def __init__(self, dtype, kv_in, g1, null_kv, wq, wo, nb, C):
         dev = kv_in.device
+        self.nk = xattn_keys(kv_in.shape[0], nb)
+        HK, KP = XA_HEADS * self.nk, _xattn_kp(self.nk)
         self.kv = kv_in.detach().float().contiguous()  # (nb * tokens, 2 * 512): to_kv(context)
         self.wqf, self.wof = wq.detach().float().contiguous(), wo.detach().float().contiguous()
         self.nkv = null_kv.detach().float().contiguous()
         self.g1f = g1.detach().float().contiguous()
-        self.at = torch.empty(nb, C, 24, dtype=torch.float32, device=dev)
+        self.at = torch.empty(nb, C, HK, dtype=torch.float32, device=dev)
         self.vt = torch.empty_like(self.at)
         Cp = (C + 31) // 32 * 32  # operand images padded to whole 32-channel MFMA tiles
-        self.Kt = torch.empty(nb, 32, Cp, dtype=dtype, device=dev)
-        self.KtT = torch.empty(nb, Cp, 32, dtype=dtype, device=dev)
-        self.Vt = torch.empty(nb, Cp, 32, dtype=dtype, device=dev)
-        self.VtT = torch.empty(nb, 32, Cp, dtype=dtype, device=dev)
-        self.colsum = torch.empty(nb, 32, dtype=torch.float32, device=dev)
+        self.Kt = torch.empty(nb, KP, Cp, dtype=dtype, device=dev)
+        self.KtT = torch.empty(nb, Cp, KP, dtype=dtype, device=dev)
+        self.Vt = torch.empty(nb, Cp, KP, dtype=dtype, device=dev)
+        self.VtT = torch.empty(nb, KP, Cp, dtype=dtype, device=dev)
+        self.colsum = torch.empty(nb, KP, dtype=torch.float32, device=dev)
         self.nb, self.C, self.dtype = nb, C, dtype
         self.batched = False  # set by xattn_fold_batched: backward may be deferred
 
@@ -2093,10 +2133,14 @@ class XattnFold:
                                                    self.VtT, self.colsum)), self.nb, self.C)
 
     def run(self):
-        call("dv_xattn_fold", _lib.DV_BF16 if self.dtype == torch.bfloat16 else _lib.DV_F32,
-             ptr(self.wqf), ptr(self.wof), ptr(self.kv), ptr(self.nkv), ptr(self.g1f), ptr(self.at),
-             ptr(self.vt), ptr(self.Kt), ptr(self.KtT), ptr(self.Vt), ptr(self.VtT), ptr(self.colsum),
-             self.nb, self.C, ctypes_float(XA_DH ** -0.5), stream())
+        args = (_lib.DV_BF16 if self.dtype == torch.bfloat16 else _lib.DV_F32,
+                ptr(self.wqf), ptr(self.wof), ptr(self.kv), ptr(self.nkv), ptr(self.g1f), ptr(self.at),
+                ptr(self.vt), ptr(self.Kt), ptr(self.KtT), ptr(self.Vt), ptr(self.VtT), ptr(self.colsum),
+                self.nb, self.C)
+        if self.nk == 3:
+            call("dv_xattn_fold", *args, ctypes_float(XA_DH ** -0.5), stream())
+        else:
+            call("dv_xattn_fold_nk", *args, self.nk, ctypes_float(XA_DH ** -0.5), stream())
 
 
 def xattn_fold_batched(folds):
@@ -2104,12 +2148,18 @@ def xattn_fold_batched(folds):
     folds = list(folds)
     for f in folds:
         f.batched = True
-    for i in range(0, len(folds), 24):  # DV_FOLD_MAX
-        part = folds[i:i + 24]
-        jobs = (DvFoldJob * len(part))(*[f.job() for f in part])
-        call("dv_xattn_fold_batched",
-             _lib.DV_BF16 if part[0].dtype == torch.bfloat16 else _lib.DV_F32,
-             ctypes.cast(jobs, ctypes.c_void_p), len(part), ctypes_float(XA_DH ** -0.5), stream())
+    for nk in sorted({f.nk for f in folds}):  # a launch runs one key count
+        same = [f for f in folds if f.nk == nk]
+        for i in range(0, len(same), 24):  # DV_FOLD_MAX
+            part = same[i:i + 24]
+            jobs = (DvFoldJob * len(part))(*[f.job() for f in part])
+            dtc = _lib.DV_BF16 if part[0].dtype == torch.bfloat16 else _lib.DV_F32
+            if nk == 3:
+                call("dv_xattn_fold_batched", dtc, ctypes.cast(jobs, ctypes.c_void_p), len(part),
+                     ctypes_float(XA_DH ** -0.5), stream())
+            else:
+                call("dv_xattn_fold_batched_nk", dtc, ctypes.cast(jobs, ctypes.c_void_p), len(part), nk,
+                     ctypes_float(XA_DH ** -0.5), stream())
 
 
 class CrossAttnFn(torch.autograd.Function):
@@ -2127,19 +2177,27 @@ class CrossAttnFn(torch.autograd.Function):
         if fold is None:
             fold = XattnFold(dtype, kv_in, g1, null_kv, wq, wo, nb, C)
             fold.run()
+        nk = fold.nk
+        if nk != xattn_keys(kv_in.shape[0], nb):
+            raise _lib.DVError("cross attention: the fold was made for another key count")
+        KP = _xattn_kp(nk)
         kv, wqf, wof, nkv, g1f = fold.kv, fold.wqf, fold.wof, fold.nkv, fold.g1f
         at, vt, Kt, KtT, Vt, VtT, colsum = (fold.at, fold.vt, fold.Kt, fold.KtT, fold.Vt, fold.VtT,
                                             fold.colsum)
         g2f = g2.detach().float().contiguous()
         out = torch.empty(nf, h, w, C, dtype=dtype, device=dev)
         stats = torch.empty(ntok, 4, dtype=torch.float32, device=dev)
-        pbuf = torch.empty(ntok, 32, dtype=dtype, device=dev)
-        call("dv_xattn_fwd", dt(x), ptr(x), cl_ld(x), ptr(out), C, ntok, P, C, ptr(Kt), ptr(Vt),
-             ptr(colsum), ptr(g2f), ctypes_float(eps), ptr(stats), ptr(pbuf), stream())
+        pbuf = torch.empty(ntok, KP, dtype=dtype, device=dev)
+        if nk == 3:
+            call("dv_xattn_fwd", dt(x), ptr(x), cl_ld(x), ptr(out), C, ntok, P, C, ptr(Kt), ptr(Vt),
+                 ptr(colsum), ptr(g2f), ctypes_float(eps), ptr(stats), ptr(pbuf), stream())
+        else:
+            call("dv_xattn_fwd_nk", dt(x), ptr(x), cl_ld(x), ptr(out), C, ntok, P, C, nk, ptr(Kt),
+                 ptr(Vt), ptr(colsum), ptr(g2f), ctypes_float(eps), ptr(stats), ptr(pbuf), stream())
         ctx.save_for_backward(x, g1f, g2f, nkv, wqf, wof, kv, at, vt, KtT, Vt, VtT,
                               colsum, stats, pbuf)
         ctx.params = (g1, null_kv, wq, wo, g2)
-        ctx.meta = (nb, eps, fold.batched)
+        ctx.meta = (nb, eps, fold.batched, nk)
         return out
 
     @staticmethod
@@ -2147,7 +2205,8 @@ class CrossAttnFn(torch.autograd.Function):
         (x, g1f, g2f, nkv, wqf, wof, kv, at, vt, KtT, Vt, VtT, colsum, stats,
          pbuf) = ctx.saved_tensors
         g1p, nullp, wqp, wop, g2p = ctx.params
-        nb, eps, defer = ctx.meta
+        nb, eps, defer, nk = ctx.meta
+        KP = _xattn_kp(nk)
         nf, h, w, C = x.shape
         ntok = nf * h * w
         P = ntok // nb
@@ -2155,26 +2214,31 @@ class CrossAttnFn(torch.autograd.Function):
         dy, lddy = _grad_view(dy)
         dx = torch.empty(nf, h, w, C, dtype=dtype, device=dev)
         dobuf = torch.empty(ntok, C, dtype=dtype, device=dev)
-        dsbuf = torch.empty(ntok, 32, dtype=dtype, device=dev)
-        p2buf = torch.empty(ntok, 32, dtype=dtype, device=dev)
-        wsR, wsV, wsQ, mcorr = _xattn_workspace(nb, C, dev, owner=wqp if defer else None)
+        dsbuf = torch.empty(ntok, KP, dtype=dtype, device=dev)
+        p2buf = torch.empty(ntok, KP, dtype=dtype, device=dev)
+        wsR, wsV, wsQ, mcorr = _xattn_workspace(nb, C, dev, owner=wqp if defer else None, KP=KP)
         ldx = cl_ld(x)
-        call("dv_xattn_bwd_tokens", dt(x), ptr(dy), lddy, ptr(x), ldx, ptr(dx), C, ntok, P, C,
-             ptr(KtT), ptr(Vt), ptr(VtT), ptr(colsum), ptr(g2f), ptr(stats), ptr(pbuf), ptr(dobuf),
-             ptr(dsbuf), ptr(p2buf), stream())
+        if nk == 3:
+            call("dv_xattn_bwd_tokens", dt(x), ptr(dy), lddy, ptr(x), ldx, ptr(dx), C, ntok, P, C,
+                 ptr(KtT), ptr(Vt), ptr(VtT), ptr(colsum), ptr(g2f), ptr(stats), ptr(pbuf), ptr(dobuf),
+                 ptr(dsbuf), ptr(p2buf), stream())
+        else:
+            call("dv_xattn_bwd_tokens_nk", dt(x), ptr(dy), lddy, ptr(x), ldx, ptr(dx), C, ntok, P, C, nk,
+                 ptr(KtT), ptr(Vt), ptr(VtT), ptr(colsum), ptr(g2f), ptr(stats), ptr(pbuf), ptr(dobuf),
+                 ptr(dsbuf), ptr(p2buf), stream())
         # per-batch token reductions: R = dS'^T X, V' = P^T dO, Q = P'^T dY (three batched
         # GEMMs of one shape, one launch)
         probs = ((dsbuf, x, ldx, wsR), (pbuf, dobuf, C, wsV), (p2buf, dy, lddy, wsQ))
         pa = (ctypes.c_void_p * 3)(*(a_.data_ptr() for a_, _, _, _ in probs))
-        la = (ctypes.c_int * 3)(32, 32, 32)
+        la = (ctypes.c_int * 3)(KP, KP, KP)
         pb = (ctypes.c_void_p * 3)(*(b_.data_ptr() for _, b_, _, _ in probs))
         lb = (ctypes.c_int * 3)(*(ldb for _, _, ldb, _ in probs))
         po = (ctypes.c_void_p * 3)(*(o_.data_ptr() for _, _, _, o_ in probs))
-        _launch(gemm_wgrad_name(_lib.dtype_name(x), ntok, 32, C, max(32, ldx, C, lddy)),
-                3 * 2.0 * ntok * 32 * C, 0,
-                lambda: call("dv_gemm_tn_batched_multi", dt(x), 3, pa, la, pb, lb, po, P, nb, 32, C,
+        _launch(gemm_wgrad_name(_lib.dtype_name(x), ntok, KP, C, max(KP, ldx, C, lddy)),
+                3 * 2.0 * ntok * KP * C, 0,
+                lambda: call("dv_gemm_tn_batched_multi", dt(x), 3, pa, la, pb, lb, po, P, nb, KP, C,
                              stream()))
-        dat = torch.empty(nb, C, 24, dtype=torch.float32, device=dev)
+        dat = torch.empty(nb, C, XA_HEADS * nk, dtype=torch.float32, device=dev)
         dvt = torch.empty_like(dat)
         s1, s2 = _grad_out(g1p), _grad_out(g2p)
         if s1 is not None and s2 is not None and s1[1] == s2[1]:
@@ -2195,12 +2259,16 @@ class CrossAttnFn(torch.autograd.Function):
                                            dvt, dg1, dg2, dwq, dwo, dkv, dnull)),
                                nb, C, acc_g, acc_w)
             _FOLD_BWD_PENDING.append((job, (wsR, wsV, wsQ, mcorr, at, vt, g1f, wqf, wof, kv, nkv, dat,
-                                            dvt, dg1, dg2, dwq, dwo, dkv, dnull)))
+                                            dvt, dg1, dg2, dwq, dwo, dkv, dnull), nk))
         else:
-            call("dv_xattn_fold_bwd", ptr(wsR), ptr(wsV), ptr(wsQ), ptr(mcorr), ptr(at), ptr(vt),
-                 ptr(g1f), ptr(wqf), ptr(wof), ptr(kv), ptr(nkv), ptr(dat), ptr(dvt), ptr(dg1),
-                 ptr(dg2), ptr(dwq), ptr(dwo), ptr(dkv), ptr(dnull), nb, C, ctypes_float(XA_DH ** -0.5),
-                 acc_g, acc_w, stream())
+            args = (ptr(wsR), ptr(wsV), ptr(wsQ), ptr(mcorr), ptr(at), ptr(vt),
+                    ptr(g1f), ptr(wqf), ptr(wof), ptr(kv), ptr(nkv), ptr(dat), ptr(dvt), ptr(dg1),
+                    ptr(dg2), ptr(dwq), ptr(dwo), ptr(dkv), ptr(dnull), nb, C)
+            if nk == 3:
+                call("dv_xattn_fold_bwd", *args, ctypes_float(XA_DH ** -0.5), acc_g, acc_w, stream())
+            else:
+                call("dv_xattn_fold_bwd_nk", *args, nk, ctypes_float(XA_DH ** -0.5), acc_g, acc_w,
+                     stream())
         return (dx, dkv, dg1 if ret_g else None, None if direct else dnull,
                 None if direct else dwq, None if direct else dwo,
                 dg2 if ret_g else None, None, None, None)
@@ -2216,7 +2284,7 @@ def cross_attention(x, context, g1, null_kv, wq, wkv, wo, g2, nb, eps, kv=None, 
     (linear_group over every block sharing the context); else computed here.
     fold: this block's XattnFold when the caller batched the folds."""
     if kv is None:
-        kv = linear_group(context.float().reshape(-1, context.shape[-1]), [wkv], [None])[0]
+        kv = linear_group_rows(context.float().reshape(-1, context.shape[-1]), [wkv], [None])[0]
     return CrossAttnFn.apply(x, kv, g1, null_kv, wq, wo, g2, nb, eps, fold)
 
 

@@ -628,6 +628,42 @@ int dv_xattn_fold_bwd(float* wsR, float* wsV, float* wsQ, float* mcorr,
                       float* dnull, int nb, int C, float scale, int acc_g, int acc_w,
                       void* stream);
 
+/* ---- 3 or 7 keys per head (ABI 7) ----------------------------------------
+ * The same six calls with the key count nk = 1 + context tokens per clip:
+ * 3 (null kv + 2 time tokens; what the calls above run) or 7 (+ 4 video
+ * tokens, Unet3D(cond_on_video_embeds=True)).  Any other nk is DV_ERR_INVALID.
+ * With HK = 8 * nk and KP = 32 * ((nk + 1) / 4) (24 / 32, 56 / 64):
+ *   kv [nb][nk-1][1024], at/vt/dat/dvt [nb][C][HK], Kt,VtT [nb][KP][Cp],
+ *   KtT,Vt [nb][Cp][KP], colsum/mcorr [nb][KP], pbuf/dsbuf/p2buf [ntok][KP],
+ *   wsR/wsV/wsQ [nb][KP][C] (the dv_gemm_tn_batched_multi reductions run with m = KP),
+ *   dkv [nb][nk-1][1024].
+ * Key j of head h is row k' = 32 * (j / 4) + 4 * h + j % 4 of the padded
+ * images: one 32-row MFMA accumulator tile per 4 keys, so a lane holds every
+ * logit of the heads it owns.  Every job of a batched
+ * call has the same nk.                                                      */
+int dv_xattn_fold_nk(int dtype, const float* wq, const float* wo, const float* kv,
+                     const float* null_kv, const float* g1, float* at, float* vt, void* Kt,
+                     void* KtT, void* Vt, void* VtT, float* colsum, int nb, int C, int nk,
+                     float scale, void* stream);
+int dv_xattn_fold_batched_nk(int dtype, const DvFoldJob* jobs, int n, int nk, float scale,
+                             void* stream);
+int dv_xattn_fwd_nk(int dtype, const void* x, int ldx, void* out, int ldo, long long ntok,
+                    long long P, int C, int nk, const void* Kt, const void* Vt,
+                    const float* colsum, const float* g2, float eps, float* stats, void* pbuf,
+                    void* stream);
+int dv_xattn_bwd_tokens_nk(int dtype, const void* dy, int lddy, const void* x, int ldx, void* dx,
+                           int lddx, long long ntok, long long P, int C, int nk, const void* KtT,
+                           const void* Vt, const void* VtT, const float* colsum, const float* g2,
+                           const float* stats, const void* pbuf, void* dobuf, void* dsbuf,
+                           void* p2buf, void* stream);
+int dv_xattn_fold_bwd_nk(float* wsR, float* wsV, float* wsQ, float* mcorr, const float* at,
+                         const float* vt, const float* g1, const float* wq, const float* wo,
+                         const float* kv, const float* null_kv, float* dat, float* dvt,
+                         float* dg1, float* dg2, float* dwq, float* dwo, float* dkv, float* dnull,
+                         int nb, int C, int nk, float scale, int acc_g, int acc_w, void* stream);
+int dv_xattn_fold_bwd_batched_nk(const DvFoldBwdJob* jobs, int n, int nk, float scale,
+                                 void* stream);
+
 /* ---- mid self-attention (Unet3D.mid_attn = Residual(Attention(mid_dim)),
  * dalle2_video.py:431, 551, 921-922; dalle2-pytorch Attention: 16 heads x 32,
  * ONE shared k/v head (multi-query), learned null k/v at key 0, q scaled
