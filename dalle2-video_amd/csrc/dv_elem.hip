@@ -1075,6 +1075,69 @@ __global__ void blur_kernel(const float* x, float* y, long long planes, int H, i
   }
 }
 
+// ---- self-conditioning (Unet3D(self_cond=True), dalle2_video.py:738-745,
+// 1969-1983): the first pass's prediction rides as extra input channels of
+// the training input.  One thread owns a pixel, so a channels-last row is
+// written once, with 16-byte stores.
+
+// element c of pixel p of a channels-last source (f32 or bf16); NULL: zero
+__device__ __forceinline__ float sc_load(const void* sc, int ldsc, int sc_bf16, long long p, int c) {
+  if (!sc) return 0.f;
+  return sc_bf16 ? (float)((const bf16*)sc)[p * ldsc + c] : ((const float*)sc)[p * ldsc + c];
+}
+
+// eight consecutive channels of a row, 16-byte stores (dst is 16-byte aligned:
+// the row stride is a multiple of 8 elements)
+__device__ __forceinline__ void store_row8(float* dst, const float* v) {
+  f32x4 lo, hi;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    lo[j] = v[j];
+    hi[j] = v[4 + j];
+  }
+  *(f32x4*)dst = lo;
+  *(f32x4*)(dst + 4) = hi;
+}
+__device__ __forceinline__ void store_row8(bf16* dst, const float* v) {
+  bf16x8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = (bf16)v[j];  // round to nearest even
+  *(bf16x8*)dst = r;
+}
+
+// q_sample_kernel with Csc self-conditioning channels after the C noised ones
+template <typename T>
+__global__ void q_sample_sc_kernel(const float* x0, const float* noise, const long long* t,
+                                   const float* sa, const float* s1m, const void* sc, int ldsc,
+                                   int sc_bf16, T* y, int B, int C, int Csc, int T_, int HW, int cpad,
+                                   int normalize, int nt) {
+  const long long npix = (long long)B * T_ * HW;
+  GRID_STRIDE(p, npix) {
+    const int hw = (int)(p % HW);
+    const long long ft = p / HW;
+    const int tt = (int)(ft % T_), b = (int)(ft / T_);
+    const long long ti = t[b];
+    const bool ok = ti >= 0 && ti < nt;  // as q_sample_kernel: NaN, no read past the table
+    const float a = ok ? sa[ti] : __builtin_nanf(""), s = ok ? s1m[ti] : __builtin_nanf("");
+    for (int c0 = 0; c0 < cpad; c0 += 8) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = c0 + j;
+        v[j] = 0.f;
+        if (c < C) {
+          const long long i = (((long long)b * C + c) * T_ + tt) * HW + hw;
+          const float xs = normalize ? x0[i] * 2.f - 1.f : x0[i];
+          v[j] = a * xs + s * noise[i];
+        } else if (c < C + Csc) {
+          v[j] = sc_load(sc, ldsc, sc_bf16, p, c - C);
+        }
+      }
+      store_row8(y + p * cpad + c0, v);
+    }
+  }
+}
+
 }  // namespace
 
 #define DISPATCH(dtype, KERNEL_CALL_F32, KERNEL_CALL_BF16) \
@@ -1384,6 +1447,31 @@ extern "C" int dv_ddim_step(int dtype, const float* x, const void* eps, int ld, 
            (ddim_step_kernel<float, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, t_next, alphas_cumprod, eta, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
            (ddim_step_kernel<bf16, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, t_next, alphas_cumprod, eta, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
   return check_launch("ddim_step");
+}
+
+// ---- self-conditioning (ABI 8) ----
+
+static bool dtype_ok(int d) { return d == DV_F32 || d == DV_BF16; }
+
+extern "C" int dv_q_sample_sc(int dtype, const float* x0, const float* noise, const long long* t,
+                              const float* sqrt_ac, const float* sqrt_1m_ac, const void* self_cond,
+                              int ldsc, int sc_dtype, void* y, int B, int C, int Csc, int T, int H,
+                              int W, int cpad, int normalize, int num_timesteps, void* stream) {
+  DV_REQUIRE(x0 && noise && t && sqrt_ac && sqrt_1m_ac && y && num_timesteps > 0 && B > 0 && C > 0 &&
+                 T > 0 && H > 0 && W > 0 && Csc >= 0,
+             "bad arguments");
+  DV_REQUIRE(dtype_ok(dtype), "unknown dtype");
+  DV_REQUIRE(cpad % 8 == 0 && (long long)C + Csc <= cpad, "C + Csc <= cpad and cpad % 8 == 0");
+  DV_REQUIRE(!self_cond || (dtype_ok(sc_dtype) && ldsc >= Csc), "self_cond is channels-last f32 / bf16 with ldsc >= Csc");
+  DV_REQUIRE((uintptr_t)y % 16 == 0, "y must be 16-byte aligned");
+  const long long npix = (long long)B * T * H * W;
+  hipStream_t st = (hipStream_t)stream;
+  const int scb = sc_dtype == DV_BF16;
+  if (dtype == DV_F32)
+    q_sample_sc_kernel<float><<<grid_for(npix), 256, 0, st>>>(x0, noise, t, sqrt_ac, sqrt_1m_ac, self_cond, ldsc, scb, (float*)y, B, C, Csc, T, H * W, cpad, normalize, num_timesteps);
+  else
+    q_sample_sc_kernel<bf16><<<grid_for(npix), 256, 0, st>>>(x0, noise, t, sqrt_ac, sqrt_1m_ac, self_cond, ldsc, scb, (bf16*)y, B, C, Csc, T, H * W, cpad, normalize, num_timesteps);
+  return check_launch("q_sample_sc");
 }
 
 extern "C" int dv_dyn_thres(int dtype, const float* x, const void* pred, int ld, const long long* t,

@@ -107,6 +107,18 @@ def _compute_dtype(module, ref: torch.Tensor):
     return torch.float32
 
 
+def _self_cond_f32_only(dtype):
+    """Self-conditioned unets run in f32 only: a bf16 self-conditioned sampling
+    loop at the benchmark clip shape ended in a GPU memory-access fault whose
+    cause is not known, and bf16 is what sends a 6-channel input
+    through the direct cross-embed kernels at a width no test has run.  Every
+    entry point refuses before it launches anything."""
+    if dtype != torch.float32:
+        raise NotImplementedError(
+            "Unet3D(self_cond=True) runs in f32 only on MI355X for now: call it outside "
+            "torch.autocast and leave unet.compute_dtype unset (trainer: amp=False)")
+
+
 def _ln_eps(dtype):
     # dalle2-pytorch LayerNorm: eps=1e-5 in f32, fp16_eps=1e-3 otherwise
     return 1e-5 if dtype == torch.float32 else 1e-3
@@ -565,7 +577,7 @@ class Unet3D(nn.Module):
                            memory_efficient=memory_efficient,
                            cross_embed_downsample=cross_embed_downsample,
                            combine_upsample_fmaps=combine_upsample_fmaps,
-                           cond_on_text_encodings=cond_on_text_encodings, self_cond=self_cond,
+                           cond_on_text_encodings=cond_on_text_encodings,
                            lowres_noise_cond=lowres_noise_cond,
                            scale_skip_connection=scale_skip_connection,
                            cosine_sim_self_attn=cosine_sim_self_attn,
@@ -580,6 +592,12 @@ class Unet3D(nn.Module):
         self.channels = channels
         self.channels_out = default(channels_out, channels)
         init_channels = channels * (1 + int(lowres_cond) + int(self_cond))
+        if self_cond and init_channels > 8:
+            # the direct cross-embed kernels (and the padded input row) take cin <= 8
+            raise NotImplementedError(
+                f"Unet3D(self_cond=True): channels * (1 + self_cond + lowres_cond) = {channels} * "
+                f"(1 + {int(self_cond)} + {int(lowres_cond)}) = {init_channels} input channels exceed "
+                "the 8 of the MI355X cross-embed kernels")
         init_dim = default(init_dim, dim)
         self.init_conv = CrossEmbedLayer3D(init_channels, dim_out=init_dim,
                                            kernel_sizes=init_cross_embed_kernel_sizes, stride=1)
@@ -705,6 +723,7 @@ class Unet3D(nn.Module):
         return self.__class__(**kw)
 
     def forward_with_cond_scale(self, *args, cond_scale=1.0, **kwargs):
+        # (self_cond, when given, rides in kwargs: both forwards read it)
         logits = self.forward(*args, **kwargs)
         if cond_scale == 1:
             return logits
@@ -792,7 +811,11 @@ class Unet3D(nn.Module):
                    text_cond_drop_prob=0.0, video_embed=None):
         """Core denoiser on channels-last frames x (batch*T, H, W, C8); returns
         channels-last (batch*T, H, W, channels_out).  video_embed (batch, E): used
-        (and required) by a unet built with cond_on_video_embeds=True."""
+        (and required) by a unet built with cond_on_video_embeds=True.  x is the
+        assembled input: for a self-conditioned unet its channels are
+        [ x | self_cond | lowres ] (Unet3D.forward / ops.q_sample_cl)."""
+        if self.self_cond:
+            _self_cond_f32_only(x.dtype)
         if getattr(self, "fp8", False) and not torch.is_grad_enabled():
             with ops.mx8_convs(attention=getattr(self, "fp8_attention", False)):
                 return self._forward_cl(x, time, batch=batch, lowres_cl=lowres_cl,
@@ -865,7 +888,17 @@ class Unet3D(nn.Module):
             raise AssertionError("lowres_noise_cond must be set to True on instantiation of the "
                                  "unet in order to conditiong on lowres noise")
         dt = _compute_dtype(self, x)
-        xin = torch.cat((x, lowres_cond_video), dim=1) if exists(lowres_cond_video) else x
+        if self.self_cond:
+            _self_cond_f32_only(dt)
+            # dalle2_video.py:738-745: cat(x, self_cond or zeros, lowres)
+            if exists(self_cond) and tuple(self_cond.shape) != (batch, self.channels, *x.shape[2:]):
+                raise ValueError(f"self_cond must be {(batch, self.channels, *x.shape[2:])}, got "
+                                 f"{tuple(self_cond.shape)}")
+            sc = self_cond.detach().to(x.dtype) if exists(self_cond) else torch.zeros_like(x)
+            xin = torch.cat((x, sc, lowres_cond_video), dim=1) if exists(lowres_cond_video) \
+                else torch.cat((x, sc), dim=1)
+        else:
+            xin = torch.cat((x, lowres_cond_video), dim=1) if exists(lowres_cond_video) else x
         xcl = ops.to_cl(xin, dt)
         lcl = ops.to_cl(lowres_cond_video, dt) if exists(lowres_cond_video) else None
         y = self.forward_cl(xcl, time, batch=batch, lowres_cl=lcl,
@@ -973,7 +1006,10 @@ class _DenoiseStepGraph:
     launches and draws it issued before either option existed.
 
     For a unet built with cond_on_video_embeds=True, `video_embed` is a third
-    fixed device buffer read by every forward of the step."""
+    fixed device buffer read by every forward of the step.
+
+    A unet built with self_cond=True has no captured step: its loops run
+    eagerly (VideoDecoder._step_graphs) and this class refuses it."""
 
     EAGER_CALLS = 2
 
@@ -993,6 +1029,9 @@ class _DenoiseStepGraph:
         self.dyn_percentile = dyn_percentile if clip_denoised else None
         self.dyn_s = (torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
                       if exists(self.dyn_percentile) else None)
+        if getattr(unet, "self_cond", False):
+            raise NotImplementedError("a self-conditioned unet has no captured denoise step: sample it with "
+                                      "the eager loops (VideoDecoder does, whatever sample_graphs says)")
         self.calls = 0
         self.graph = None
 
@@ -1242,6 +1281,10 @@ class VideoDecoder(nn.Module):
         # (DV_SAMPLE_GRAPHS=0: launch every step eagerly)
         import os
         self.sample_graphs = os.environ.get("DV_SAMPLE_GRAPHS", "1") != "0"
+        # self-conditioned unets: p_losses draws random.random() < 0.5 per call
+        # (dalle2_video.py:1971); True / False pins the decision (the trainer's
+        # graphed calls draw it themselves, as for LowresVideoConditioner.forced_blur)
+        self.forced_self_cond = None
 
     @property
     def device(self):
@@ -1279,18 +1322,42 @@ class VideoDecoder(nn.Module):
         noise = default(noise, lambda: torch.randn_like(x_start))
         dt = _compute_dtype(unet, x_start)
         B, C, T = x_start.shape[:3]
-        # x_t = sqrt(ac[t]) * (2 x0 - 1) + sqrt(1 - ac[t]) * eps, written channels-last
-        xn = ops.q_sample_cl(x_start, noise, times, noise_scheduler.sqrt_alphas_cumprod,
-                             noise_scheduler.sqrt_one_minus_alphas_cumprod, dt,
-                             normalize=not is_latent_diffusion)
-        lcl = None
-        if exists(lowres_cond_video):
-            lv = lowres_cond_video if is_latent_diffusion else self.normalize_video(lowres_cond_video)
-            lcl = ops.to_cl(lv, dt)
-            lc = lv.shape[1]
-            if C + lc > xn.shape[-1]:
-                raise DVError("lowres conditioning needs C + C_lowres <= 8 channels")
-            xn[..., C:C + lc] = lcl[..., :lc]  # the channel concat (dalle2_video.py:744)
+        # a self-conditioned unet reads C more channels between x_t and the low-res clip
+        csc = C if getattr(unet, "self_cond", False) else 0
+        if csc:
+            _self_cond_f32_only(dt)
+        low = []  # [channels-last low-res clip], converted once (after the first q_sample)
+
+        def noised_input(self_cond_cl):
+            # x_t = sqrt(ac[t]) * (2 x0 - 1) + sqrt(1 - ac[t]) * eps, written channels-last
+            xn = ops.q_sample_cl(x_start, noise, times, noise_scheduler.sqrt_alphas_cumprod,
+                                 noise_scheduler.sqrt_one_minus_alphas_cumprod, dt,
+                                 normalize=not is_latent_diffusion, self_cond_cl=self_cond_cl, csc=csc)
+            if not exists(lowres_cond_video):
+                return xn, None
+            if not low:
+                lv = lowres_cond_video if is_latent_diffusion else self.normalize_video(lowres_cond_video)
+                low.append(ops.to_cl(lv, dt))
+            lcl, lc = low[0], lowres_cond_video.shape[1]
+            if C + csc + lc > xn.shape[-1]:
+                raise DVError("lowres conditioning needs C + C_self_cond + C_lowres <= 8 channels")
+            xn[..., C + csc:C + csc + lc] = lcl[..., :lc]  # the channel concat (dalle2_video.py:744)
+            return xn, lcl
+
+        self_cond_cl = None
+        # (the host draw is made for self-conditioned unets only: every other
+        # decoder's random stream is what it was)
+        if csc and (self.forced_self_cond if self.forced_self_cond is not None
+                    else random.random() < 0.5):
+            # dalle2_video.py:1971-1975: the unet's own prediction on the zero
+            # self-cond input, without gradient and without conditioning dropout;
+            # the raw output whatever the objective.  _forward_cl:
+            # a training pass never runs the fp8 sampling convs, whatever unet.fp8 says
+            with torch.no_grad():
+                xn, lcl = noised_input(None)
+                self_cond_cl = unet._forward_cl(xn, times, batch=B, lowres_cl=lcl,
+                                                video_embed=video_embed).detach()
+        xn, lcl = noised_input(self_cond_cl)
         pred = unet.forward_cl(xn, times, batch=B, lowres_cl=lcl,
                                video_cond_drop_prob=self.video_cond_drop_prob,
                                text_cond_drop_prob=self.text_cond_drop_prob,
@@ -1347,13 +1414,20 @@ class VideoDecoder(nn.Module):
         assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
         pred = unet.forward_with_cond_scale(x, t, video_embed=video_embed,
                                             cond_scale=cond_scale,
-                                            lowres_cond_video=lowres_cond_vid)
+                                            lowres_cond_video=lowres_cond_vid,
+                                            **self._self_cond_kwargs(unet, self_cond))
         noise = default(noise, lambda: torch.randn_like(x))
         objective = ops.objective_name(predict_x_start, predict_v)
         out, x0 = ops.p_sample_step(x, pred, noise, t, noise_scheduler, clip_denoised, objective=objective,
                                     dyn_scale=self._dyn_scale(x, pred, t, noise_scheduler, objective,
                                                               clip_denoised, ddim=False))
         return out, x0
+
+    @staticmethod
+    def _self_cond_kwargs(unet, self_cond):
+        """self_cond= for the forwards of a self-conditioned unet (the previous
+        step's x0, NCTHW; None: zeros); nothing for any other denoiser."""
+        return dict(self_cond=self_cond) if getattr(unet, "self_cond", False) else {}
 
     def _dyn_scale(self, x, pred, t, noise_scheduler, objective, clip_denoised, ddim):
         """The per-sample threshold of dynamic_threshold (:1531-1549), or None
@@ -1363,6 +1437,12 @@ class VideoDecoder(nn.Module):
             return None
         return ops.dynamic_threshold_scale(x, pred, t, noise_scheduler, objective,
                                            self.dynamic_thres_percentile, ddim=ddim)
+
+    def _step_graphs(self, unet, vid):
+        """Does this loop replay a captured step?  Not for a self-conditioned
+        unet: its step (x0 handed from one step to the next) is not captured,
+        the loop launches every step."""
+        return vid.is_cuda and self.sample_graphs and not getattr(unet, "self_cond", False)
 
     def _dyn_percentile(self):
         return self.dynamic_thres_percentile if self.use_dynamic_thres else None
@@ -1380,7 +1460,7 @@ class VideoDecoder(nn.Module):
         vid = torch.randn(shape, device=self.device)
         if not is_latent_diffusion:
             lowres_cond_vid = maybe(self.normalize_video)(lowres_cond_vid)
-        if vid.is_cuda and self.sample_graphs:
+        if self._step_graphs(unet, vid):
             with ops.private_pack_cache():
                 step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
                                          lowres_cond_vid, clip_denoised,
@@ -1392,26 +1472,29 @@ class VideoDecoder(nn.Module):
             return self.unnormalize_video(vid)
         # the eager loop packs its (unchanging) weights into a private cache too, so
         # sampling never adds entries the trainer's per-update refresh would repack
+        x_start = None  # the previous step's x0: the next step's self-conditioning (:1727)
         with (ops.private_pack_cache() if vid.is_cuda else nullcontext()):
             for time in reversed(range(0, noise_scheduler.num_timesteps)):
                 times = torch.full((b,), time, device=self.device, dtype=torch.long)
-                vid, _ = self.p_sample(unet, vid, times, video_embed=video_embed,
-                                       cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
-                                       predict_x_start=predict_x_start, predict_v=predict_v,
-                                       noise_scheduler=noise_scheduler, clip_denoised=clip_denoised)
+                vid, x_start = self.p_sample(unet, vid, times, video_embed=video_embed,
+                                             cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
+                                             self_cond=x_start,
+                                             predict_x_start=predict_x_start, predict_v=predict_v,
+                                             noise_scheduler=noise_scheduler, clip_denoised=clip_denoised)
         return self.unnormalize_video(vid)
 
     @torch.no_grad()
     def p_sample_ddim(self, unet, x, t, t_next, video_embed, noise_scheduler, eta, cond_scale=1.0,
                       lowres_cond_vid=None, clip_denoised=True, noise=None, predict_x_start=False,
-                      predict_v=False):
+                      predict_v=False, self_cond=None):
         """One DDIM step t -> t_next (the body of the loop at
         dalle2_video.py:1811-1876): returns (x_next, x0).  At eta == 0 no noise
         is drawn."""
         assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
         pred = unet.forward_with_cond_scale(x, t, video_embed=video_embed,
                                             cond_scale=cond_scale,
-                                            lowres_cond_video=lowres_cond_vid)
+                                            lowres_cond_video=lowres_cond_vid,
+                                            **self._self_cond_kwargs(unet, self_cond))
         if eta != 0:
             noise = default(noise, lambda: torch.randn_like(x))
         objective = ops.objective_name(predict_x_start, predict_v)
@@ -1445,7 +1528,7 @@ class VideoDecoder(nn.Module):
             vid = torch.randn(shape, device=self.device)
         if not is_latent_diffusion:
             lowres_cond_vid = maybe(self.normalize_video)(lowres_cond_vid)
-        if vid.is_cuda and self.sample_graphs:
+        if self._step_graphs(unet, vid):
             with ops.private_pack_cache():
                 step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
                                          lowres_cond_vid, clip_denoised, ddim_eta=eta,
@@ -1455,15 +1538,16 @@ class VideoDecoder(nn.Module):
                     step(time, time_next)
                 del step
             return self.unnormalize_video(vid)
+        x_start = None  # the previous step's x0: the next step's self-conditioning (:1830)
         with (ops.private_pack_cache() if vid.is_cuda else nullcontext()):
             for time, time_next in pairs:
                 times = torch.full((b,), time, device=self.device, dtype=torch.long)
                 times_next = torch.full((b,), time_next, device=self.device, dtype=torch.long)
-                vid, _ = self.p_sample_ddim(unet, vid, times, times_next, video_embed=video_embed,
-                                            noise_scheduler=noise_scheduler, eta=eta,
-                                            cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
-                                            clip_denoised=clip_denoised,
-                                            predict_x_start=predict_x_start, predict_v=predict_v)
+                vid, x_start = self.p_sample_ddim(unet, vid, times, times_next, video_embed=video_embed,
+                                                  noise_scheduler=noise_scheduler, eta=eta,
+                                                  cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
+                                                  clip_denoised=clip_denoised, self_cond=x_start,
+                                                  predict_x_start=predict_x_start, predict_v=predict_v)
         return self.unnormalize_video(vid)
 
     @torch.no_grad()

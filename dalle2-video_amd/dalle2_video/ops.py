@@ -2509,12 +2509,38 @@ def from_cl(y, B, C, T):
 # ---------------------------------------------------------------------------
 # diffusion arithmetic (q_sample, l2 loss, posterior step)
 # ---------------------------------------------------------------------------
-def q_sample_cl(x_start, noise, times, sqrt_ac, sqrt_1m_ac, dtype, normalize=True):
+def _sc_source(name, sc, npix, csc):
+    """(tensor, ld, dtype code) of a channels-last self-conditioning source:
+    frames (NF, H, W, >= csc) of npix pixels; None: zeros."""
+    if sc is None:
+        return None, 0, _lib.DV_F32
+    require_gpu(sc)
+    if sc.requires_grad:
+        raise _lib.DVError(f"{name}: the self-conditioning source carries no gradient (detach it)")
+    if csc <= 0 or sc.dim() != 4 or sc.shape[-1] < csc or sc.shape[0] * sc.shape[1] * sc.shape[2] != npix:
+        raise _lib.DVError(f"{name}: self_cond_cl {tuple(sc.shape)} is not (NF, H, W, >= {csc}) frames of "
+                           f"{npix} pixels")
+    return sc, cl_ld(sc), dt(sc)
+
+
+def q_sample_cl(x_start, noise, times, sqrt_ac, sqrt_1m_ac, dtype, normalize=True, self_cond_cl=None, csc=0):
+    """csc > 0 (a self-conditioned unet): channels [C, C + csc) of the result
+    hold self_cond_cl (channels-last, any dtype; None: zeros), still one launch."""
     require_gpu(x_start, noise, times)
     x0 = x_start.float().contiguous()
     nz = noise.float().contiguous()
     t = times.to(torch.int64).contiguous()
     B, C, T, H, W = x0.shape
+    if csc:
+        sc, ldsc, scdt = _sc_source("q_sample", self_cond_cl, B * T * H * W, csc)
+        cp = _pad8(C + csc)
+        y = torch.empty(B * T, H, W, cp, dtype=dtype, device=x0.device)
+        call("dv_q_sample_sc", _lib.DV_BF16 if dtype == torch.bfloat16 else _lib.DV_F32, ptr(x0), ptr(nz),
+             ptr(t), ptr(sqrt_ac), ptr(sqrt_1m_ac), ptr(sc), ldsc, scdt, ptr(y), B, C, csc, T, H, W, cp,
+             int(normalize), sqrt_ac.numel(), stream())
+        return y
+    if self_cond_cl is not None:
+        raise _lib.DVError("q_sample: self_cond_cl needs csc > 0")
     cp = _pad8(C)
     y = torch.empty(B * T, H, W, cp, dtype=dtype, device=x0.device)
     call("dv_q_sample", _lib.DV_BF16 if dtype == torch.bfloat16 else _lib.DV_F32, ptr(x0), ptr(nz), ptr(t),

@@ -1059,7 +1059,8 @@ class VideoDecoderTrainer(nn.Module):
 
     def _graphed_call(self, unet_number, args, kwargs, variant=None):
         """Replay (capturing on first use) forward + backward of one training
-        call; `variant` (the pinned blur decision) selects the graph."""
+        call; `variant` (the pinned blur decision, with the pinned
+        self-conditioning decision for a self-conditioned unet) selects the graph."""
         opt = getattr(self, f"optim{unet_number - 1}")
         # the deferred gradient zeros the call starts from (ops.FRESH): a call
         # right after update() overwrites the conv gradients, an accumulating
@@ -1170,12 +1171,23 @@ class VideoDecoderTrainer(nn.Module):
             # made here and pinned for this call: the graph of that decision replays,
             # and the eager warm-up calls below see the same decision
             lc.forced_blur = bool(lc.use_blur and random.random() < lc.blur_prob)
+        variant = None if lc is None else lc.forced_blur
+        self_cond = bool(getattr(self.decoder.get_unet(unet_number), "self_cond", False))
+        pinned = self.decoder.forced_self_cond  # a decision the caller pinned stays (no draw)
+        if graphable and self_cond:
+            # p_losses' one host draw per call (dalle2_video.py:1971), made here after
+            # the conditioner's and pinned the same way: the step with the extra
+            # no-grad forward and the step without it are two captured graphs
+            if pinned is None:
+                self.decoder.forced_self_cond = random.random() < 0.5
+            variant = (variant, bool(self.decoder.forced_self_cond))
         try:
             return self._forward_calls(args, kwargs, unet_number, max_batch_size, return_lowres_cond_video,
-                                       graphable, None if lc is None else lc.forced_blur)
+                                       graphable, variant)
         finally:
             if lc is not None:
                 lc.forced_blur = None
+            self.decoder.forced_self_cond = pinned
 
     def _forward_calls(self, args, kwargs, unet_number, max_batch_size, return_lowres_cond_video,
                        graphable, variant):

@@ -504,6 +504,21 @@ int dv_dyn_thres(int dtype, const float* x, const void* pred, int ld, const long
                  int objective, int num_timesteps, long long k0, float frac, float* s,
                  void* stream);
 
+/* ---- self-conditioning (ABI 8) --------------------------------------------
+ * Unet3D(self_cond=True) (dalle2_video.py:738-745) reads an estimate of the
+ * prediction as `Csc` extra input channels.  dv_q_sample_sc is dv_q_sample
+ * with channels [C, C + Csc) of y filled from a self-conditioning source: a
+ * channels-last tensor sc[p*ldsc + c], c < Csc, of dtype sc_dtype (DV_F32 /
+ * DV_BF16, independent of the output dtype); NULL stands for zeros (the
+ * reference's zeros_like default).  Channels [0, C) are those of dv_q_sample
+ * to the bit, the rest of the cpad row is zero.  cpad % 8 == 0, y 16-byte
+ * aligned.  One thread per pixel, no atomics, no workspace: the training
+ * input of a self-conditioned unet is still one launch.                      */
+int dv_q_sample_sc(int dtype, const float* x0, const float* noise, const long long* t,
+                   const float* sqrt_ac, const float* sqrt_1m_ac, const void* self_cond, int ldsc,
+                   int sc_dtype, void* y, int B, int C, int Csc, int T, int H, int W, int cpad,
+                   int normalize, int num_timesteps, void* stream);
+
 /* ---- time conditioning MLPs (Unet3D.to_time_hiddens / to_time_tokens /
  * to_time_cond, dalle2_video.py:348-357; ResnetBlock3D.time_mlp, :152-155)
  * SinusoidalPosEmb (:349): out[b] = [sin(t*f), cos(t*f)], freqs = dim/2
