@@ -1026,6 +1026,107 @@ __global__ void ddim_step_kernel(const float* x, const T* eps, int ld, const flo
   }
 }
 
+// RePaint bookkeeping of one sampling pass on the NCTHW f32 loop state, in
+// place (p_sample_loop_ddim, dalle2_video.py:1822-1828, 1878-1886).  With
+// k = the known clip (2 known - 1 when normalize), a = sqrt_ac, s = sqrt_1m_ac:
+//   masked,   FINAL     : x = k
+//   masked,   otherwise : x = a[t] k + s[t] noise                  (q_sample at t)
+//   unmasked, t_from    : x = (a[t]/a[u]) x + ((s[t] a[u] - s[u] a[t])/a[u]) noise,
+//                         u = t_from[b]      (NoiseScheduler.q_sample_from_to u -> t)
+//   unmasked, otherwise : x is not written
+// The renoise factors come from the four f32 table entries in double and are
+// rounded to f32 once: s[t] a[u] - s[u] a[t] cancels (to ~1e-3 of its terms
+// between neighbouring steps), which f32 products would turn into ~1e-5 of the
+// factor.  A sample whose t (or, with t_from, whose t_from) is out of schedule
+// has every element this call writes set to NaN; the tables are then read at 0.
+struct BlendCoef {
+  float ka, kn;  // masked:   ka k + kn noise
+  float ua, un;  // unmasked: ua x + un noise (t_from only)
+  bool ok;
+};
+template <bool FINAL>
+__device__ __forceinline__ BlendCoef blend_coef(int b, const long long* t, const long long* t_from,
+                                                const float* sa, const float* s1m, int nt) {
+  BlendCoef c{1.f, 0.f, 1.f, 0.f, true};
+  if constexpr (!FINAL) {
+    const long long t0 = t[b], u0 = t_from ? t_from[b] : 0;
+    c.ok = t0 >= 0 && t0 < nt && (!t_from || (u0 >= 0 && u0 < t0));
+    const long long ti = c.ok ? t0 : 0, ui = c.ok ? u0 : 0;
+    c.ka = sa[ti];
+    c.kn = s1m[ti];
+    if (t_from) {
+      const double at = sa[ti], au = sa[ui], st = s1m[ti], su = s1m[ui];
+      c.ua = (float)(at / au);
+      c.un = (float)((st * au - su * at) / au);
+    }
+  }
+  return c;
+}
+template <bool FINAL>
+__device__ __forceinline__ float blend_one(float x, float known, float nz, bool masked, bool renoise,
+                                           const BlendCoef& c, int normalize) {
+  float r = x;
+  if (masked) {
+    const float k = normalize ? 2.f * known - 1.f : known;
+    r = FINAL ? k : c.ka * k + c.kn * nz;
+  } else if (renoise) {
+    r = c.ua * x + c.un * nz;
+  }
+  return (c.ok || !(masked || renoise)) ? r : __builtin_nanf("");
+}
+
+// VEC: HW % 4 == 0 and every pointer aligned, so one thread owns four
+// neighbouring pixels of one frame of one channel: float4 accesses, and the
+// four mask bytes as one 32-bit word.  Otherwise one element per thread.
+template <bool VEC, bool FINAL>
+__global__ void inpaint_blend_kernel(float* x, const float* known, const unsigned char* mask,
+                                     const float* noise, const long long* t, const long long* t_from,
+                                     const float* sa, const float* s1m, int B, int C, int T_, int HW,
+                                     int normalize, int nt) {
+  const bool renoise = !FINAL && t_from != nullptr;
+  constexpr int V = VEC ? 4 : 1;
+  const int HWV = HW / V;
+  const long long n = (long long)B * C * T_ * HWV;
+  // the factors depend on the sample only: a thread forms them (two f64
+  // divisions with t_from) when its stride enters another sample, not per trip
+  int cb = -1;
+  BlendCoef c{1.f, 0.f, 1.f, 0.f, true};
+  GRID_STRIDE(i, n) {
+    const int hw = (int)(i % HWV);
+    long long r = i / HWV;
+    const int tt = (int)(r % T_);
+    r /= T_;
+    const int b = (int)(r / C);
+    const long long mi = ((long long)b * T_ + tt) * HWV + hw;
+    if constexpr (VEC) {
+      const unsigned m = reinterpret_cast<const unsigned*>(mask)[mi];
+      if (m == 0u && !renoise) continue;
+      if (b != cb) {
+        c = blend_coef<FINAL>(b, t, t_from, sa, s1m, nt);
+        cb = b;
+      }
+      float4 xv = reinterpret_cast<const float4*>(x)[i];
+      const float4 kv = reinterpret_cast<const float4*>(known)[i];
+      float4 nv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (!FINAL) nv = reinterpret_cast<const float4*>(noise)[i];
+      xv.x = blend_one<FINAL>(xv.x, kv.x, nv.x, (m & 0xffu) != 0, renoise, c, normalize);
+      xv.y = blend_one<FINAL>(xv.y, kv.y, nv.y, (m & 0xff00u) != 0, renoise, c, normalize);
+      xv.z = blend_one<FINAL>(xv.z, kv.z, nv.z, (m & 0xff0000u) != 0, renoise, c, normalize);
+      xv.w = blend_one<FINAL>(xv.w, kv.w, nv.w, (m & 0xff000000u) != 0, renoise, c, normalize);
+      reinterpret_cast<float4*>(x)[i] = xv;
+    } else {
+      const bool masked = mask[mi] != 0;
+      if (!masked && !renoise) continue;
+      if (b != cb) {
+        c = blend_coef<FINAL>(b, t, t_from, sa, s1m, nt);
+        cb = b;
+      }
+      const float nz = FINAL ? 0.f : noise[i];
+      x[i] = blend_one<FINAL>(x[i], known[i], nz, masked, renoise, c, normalize);
+    }
+  }
+}
+
 // per-frame nearest resize of NCTHW f32 planes (F.interpolate(mode="nearest"),
 // resize_image_to at dalle2_video.py:2257, 1129-1146); optional clamp
 __device__ __forceinline__ int nearest_src(int o, int in, int out) {
@@ -1447,6 +1548,35 @@ extern "C" int dv_ddim_step(int dtype, const float* x, const void* eps, int ld, 
            (ddim_step_kernel<float, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const float*)eps, ld, noise, t, t_next, alphas_cumprod, eta, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)),
            (ddim_step_kernel<bf16, DV_OBJ_EPS, false><<<grid_for(n), 256, 0, st>>>(x, (const bf16*)eps, ld, noise, t, t_next, alphas_cumprod, eta, nullptr, out, x0_out, B, C, T, H * W, clip, num_timesteps)));
   return check_launch("ddim_step");
+}
+
+// ---- inpainting (ABI 9) ----
+
+extern "C" int dv_inpaint_blend(float* x, const float* known, const unsigned char* mask,
+                                const float* noise, const long long* t, const long long* t_from,
+                                const float* sqrt_ac, const float* sqrt_1m_ac, int B, int C, int T,
+                                int H, int W, int normalize, int final, int num_timesteps,
+                                void* stream) {
+  DV_REQUIRE(x && known && mask && B > 0 && C > 0 && T > 0 && H > 0 && W > 0, "bad arguments");
+  DV_REQUIRE(final || (noise && t && sqrt_ac && sqrt_1m_ac && num_timesteps > 0),
+             "noise, t and both tables may be NULL only with final != 0");
+  DV_REQUIRE(!(final && t_from), "the final blend takes no t_from");
+  DV_REQUIRE((long long)H * W <= 0x7fffffffLL, "H * W must fit an int");
+  const int HW = H * W;
+  const long long n = (long long)B * C * T * HW;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(known) |
+                       reinterpret_cast<uintptr_t>(noise);
+  const bool vec = HW % 4 == 0 && (al & 15) == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+  hipStream_t st = (hipStream_t)stream;
+#define DV_IB(VEC, FINAL) inpaint_blend_kernel<VEC, FINAL><<<grid_for(n / (VEC ? 4 : 1), 256, 2048), 256, 0, st>>>( \
+    x, known, mask, noise, t, t_from, sqrt_ac, sqrt_1m_ac, B, C, T, HW, normalize, num_timesteps)
+  if (vec) {
+    if (final) DV_IB(true, true); else DV_IB(true, false);
+  } else {
+    if (final) DV_IB(false, true); else DV_IB(false, false);
+  }
+#undef DV_IB
+  return check_launch("inpaint_blend");
 }
 
 // ---- self-conditioning (ABI 8) ----

@@ -929,6 +929,44 @@ def resize_video_to(video, size, clamp_range=None, nearest=True):
     return ops.resize_nearest(video, size, clamp_range)
 
 
+def _nearest_index(n_in, n_out, device=None):
+    """Source index of every output position of a nearest resize n_in -> n_out:
+    floor(o * n_in / n_out) with the f32 scale F.interpolate(mode="nearest")
+    and ops.resize_nearest use, clamped to n_in - 1."""
+    o = torch.arange(n_out, device=device)
+    if n_out == n_in:
+        return o
+    if n_out == 2 * n_in:
+        return o >> 1
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    return (o.to(torch.float32) * scale.to(o.device)).floor().long().clamp_max(n_in - 1)
+
+
+def resize_mask_nearest(mask, size):
+    """Per-frame nearest resize of a (b, f, h, w) mask to size x size by the
+    index rule of resize_video_to, so a resized mask marks the pixels the
+    resized clip took from marked pixels.  Pure indexing: any device, any dtype."""
+    h, w = mask.shape[-2:]
+    if (h, w) == (size, size):
+        return mask
+    iy, ix = _nearest_index(h, size, mask.device), _nearest_index(w, size, mask.device)
+    return mask[..., iy[:, None], ix[None, :]]
+
+
+def inpaint_passes(pairs, resample_times):
+    """The passes of a RePaint loop (dalle2_video.py:1811-1883) over the
+    (time, time_next) pairs of a sampler: every pair runs `resample_times`
+    passes, and every pass but a pair's last one (and but those of the last
+    pair) ends renoised time_next -> time.  Yields (time, time_next,
+    time_from): time_from is the level the pass before was renoised from (this
+    pass's blend carries that renoise), else None."""
+    time_from = None
+    for i, (time, time_next) in enumerate(pairs):
+        for r in reversed(range(resample_times)):
+            yield time, time_next, time_from
+            time_from = time_next if (r > 0 and i < len(pairs) - 1) else None
+
+
 class LowresVideoConditioner(nn.Module):
     def __init__(self, downsample_first=True, use_blur=True, blur_prob=0.5, blur_sigma=0.6,
                  blur_kernel_size=3, use_noise=False, input_video_range=None,
@@ -1009,12 +1047,21 @@ class _DenoiseStepGraph:
     fixed device buffer read by every forward of the step.
 
     A unet built with self_cond=True has no captured step: its loops run
-    eagerly (VideoDecoder._step_graphs) and this class refuses it."""
+    eagerly (VideoDecoder._step_graphs) and this class refuses it.
+
+    Inpainting (inpaint_known / inpaint_mask, keyword-only: the known clip at
+    the loop's resolution in the input range, and its uint8 mask) puts a noise
+    draw and one ops.inpaint_blend in front of the forward.  A pass that
+    follows a renoise passes `time_from` to the call: its blend also renoises
+    the unknown region time_from -> time.  The two blends differ in one
+    pointer (the fixed device buffer `t_from`, or NULL), so each has a captured
+    graph of its own, captured at its first call after the eager ones."""
 
     EAGER_CALLS = 2
 
     def __init__(self, decoder, unet, x, video_embed, noise_scheduler, cond_scale, lowres_cond_vid,
-                 clip_denoised, ddim_eta=None, objective="eps", dyn_percentile=None):
+                 clip_denoised, ddim_eta=None, objective="eps", dyn_percentile=None, *,
+                 inpaint_known=None, inpaint_mask=None, inpaint_normalize=False):
         self.decoder, self.unet, self.x = decoder, unet, x
         self.video_embed, self.sched, self.cond_scale = video_embed, noise_scheduler, cond_scale
         if getattr(unet, "cond_on_video_embeds", False) and exists(video_embed):
@@ -1032,8 +1079,13 @@ class _DenoiseStepGraph:
         if getattr(unet, "self_cond", False):
             raise NotImplementedError("a self-conditioned unet has no captured denoise step: sample it with "
                                       "the eager loops (VideoDecoder does, whatever sample_graphs says)")
+        assert exists(inpaint_known) == exists(inpaint_mask)
+        self.inpaint_known, self.inpaint_mask = inpaint_known, inpaint_mask
+        self.inpaint_normalize = inpaint_normalize
+        self.t_from = torch.zeros_like(self.t) if exists(inpaint_known) else None
         self.calls = 0
-        self.graph = None
+        self.graph = None  # the captured step
+        self.graph_renoise = None  # the captured step whose blend renoises t_from -> t
 
     def _dyn_scale(self, pred, ddim):
         if not exists(self.dyn_percentile):
@@ -1052,8 +1104,11 @@ class _DenoiseStepGraph:
                       out=self.x, want_x0=False, objective=self.objective,
                       dyn_scale=self._dyn_scale(eps, True))
 
-    def _body(self):
+    def _body(self, renoise=False):
         x, unet = self.x, self.unet
+        if exists(self.inpaint_known):
+            ops.inpaint_blend(x, self.inpaint_known, self.inpaint_mask, torch.randn_like(x), self.t, self.sched,
+                              times_from=self.t_from if renoise else None, normalize=self.inpaint_normalize)
         if self.cond_scale == 1:
             # forward without the NCTHW round trip: the update reads the
             # channels-last prediction directly
@@ -1069,21 +1124,27 @@ class _DenoiseStepGraph:
         # (no bound method kept on self: `del step` must free the graph at once)
         (self._ddim_update if exists(self.ddim_eta) else self._ddpm_update)(eps)
 
-    def __call__(self, time, time_next=None):
+    def __call__(self, time, time_next=None, time_from=None):
         self.t.fill_(time)
         if exists(self.t_next):
             self.t_next.fill_(time_next)
+        renoise = exists(time_from)
+        if renoise:
+            assert exists(self.t_from), "time_from belongs to a step built with inpainting inputs"
+            self.t_from.fill_(time_from)
         self.calls += 1
         if self.calls <= self.EAGER_CALLS or ops.TIMER is not None:
-            self._body()
+            self._body(renoise)
             return
-        if self.graph is None:
+        slot = "graph_renoise" if renoise else "graph"
+        if getattr(self, slot) is None:
             torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self._body()
+            graph = torch.cuda.CUDAGraph()
+            setattr(self, slot, graph)
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                self._body(renoise)
                 ops.gn_graph_boundary(self.x.device)
-        self.graph.replay()
+        getattr(self, slot).replay()
 
 
 # ---------------------------------------------------------------------------
@@ -1447,40 +1508,136 @@ class VideoDecoder(nn.Module):
     def _dyn_percentile(self):
         return self.dynamic_thres_percentile if self.use_dynamic_thres else None
 
+    # ---- inpainting (RePaint, arXiv 2201.09865; dalle2_video.py:1775-1886) ----
+    @staticmethod
+    def _inpaint_requested(inpaint_video, inpaint_mask, inpaint_resample_times, unets):
+        """Is this an inpainting call?  The checks sample() and the loops
+        share: the pair comes together, the pass count is an integer >= 1 and
+        none of `unets` (the denoisers the call runs) is self-conditioned."""
+        if exists(inpaint_video) != exists(inpaint_mask):
+            raise ValueError("inpaint_video and inpaint_mask are given together or not at all")
+        if not exists(inpaint_video):
+            return False
+        if int(inpaint_resample_times) != inpaint_resample_times or inpaint_resample_times < 1:
+            raise ValueError(f"inpaint_resample_times must be an integer >= 1, got {inpaint_resample_times}")
+        if any(getattr(u, "self_cond", False) for u in unets):
+            raise NotImplementedError("inpainting with a self-conditioned unet is not implemented")
+        return True
+
+    def _prepare_inpaint(self, inpaint_video, inpaint_mask, inpaint_resample_times=5, batch_size=None,
+                         unet_numbers=None):
+        """Validates the inpainting arguments of sample() and returns
+        (video f32, mask bool (b, f, h, w)), or None when neither is given.  A
+        (b, h, w) mask is repeated over the frames.  `unet_numbers`: the unets
+        the call samples.  Needs no GPU."""
+        unet_numbers = default(unet_numbers, range(1, self.num_unets + 1))
+        if not self._inpaint_requested(inpaint_video, inpaint_mask, inpaint_resample_times,
+                                       [self.unets[n - 1] for n in unet_numbers]):
+            return None
+        if inpaint_video.dim() != 5 or inpaint_video.shape[1] != self.channels:
+            raise ValueError(f"inpaint_video must be (b, {self.channels}, f, h, w), got {tuple(inpaint_video.shape)}")
+        b, _, f, h, w = inpaint_video.shape
+        if h != w:
+            raise ValueError(f"inpaint_video must have square frames (every unet samples frame_size x frame_size), "
+                             f"got {h} x {w}")
+        if inpaint_mask.dtype != torch.bool:
+            raise ValueError(f"inpaint_mask must be a bool tensor (True: known), got {inpaint_mask.dtype}")
+        if inpaint_mask.dim() == 3:
+            inpaint_mask = inpaint_mask[:, None].expand(-1, f, -1, -1)
+        if tuple(inpaint_mask.shape) != (b, f, h, w):
+            raise ValueError(f"inpaint_mask must be {(b, f, h, w)} or {(b, h, w)} for an inpaint_video of "
+                             f"{tuple(inpaint_video.shape)}, got {tuple(inpaint_mask.shape)}")
+        if exists(batch_size) and b != batch_size:
+            raise ValueError(f"inpaint_video has batch {b}, the call samples a batch of {batch_size}")
+        for n in unet_numbers:
+            if exists(self.frame_numbers) and self.frame_numbers[n - 1] != f:
+                raise ValueError(f"inpaint_video has {f} frames, unet {n} samples {self.frame_numbers[n - 1]}")
+        return inpaint_video.float(), inpaint_mask
+
+    def _inpaint_loop_inputs(self, unet, shape, inpaint_video, inpaint_mask, inpaint_resample_times,
+                             is_latent_diffusion):
+        """(keyword inputs of the blend, resample_times) of one loop; the pair
+        comes at the loop's resolution.  (None, 1) without inpainting."""
+        if not self._inpaint_requested(inpaint_video, inpaint_mask, inpaint_resample_times, [unet]):
+            return None, 1
+        b, _, f, h, w = shape
+        if tuple(inpaint_video.shape) != tuple(shape) or tuple(inpaint_mask.shape) != (b, f, h, w):
+            raise ValueError(f"the loop samples {tuple(shape)}: inpaint_video {tuple(inpaint_video.shape)} and "
+                             f"inpaint_mask {tuple(inpaint_mask.shape)} do not match it")
+        known = inpaint_video.to(device=self.device, dtype=torch.float32).contiguous()
+        mask = inpaint_mask.to(device=self.device).ne(0).to(torch.uint8).contiguous()
+        # normalize_video, like training data, folded into the blend kernel
+        return dict(known=known, mask=mask,
+                    normalize=self.auto_normalize_video and not is_latent_diffusion), int(inpaint_resample_times)
+
+    @staticmethod
+    def _inpaint_step_kwargs(inp):
+        return dict(inpaint_known=inp["known"], inpaint_mask=inp["mask"],
+                    inpaint_normalize=inp["normalize"]) if exists(inp) else {}
+
+    def _inpaint_blend(self, vid, inp, noise_scheduler, time=None, time_from=None):
+        """The blend in front of one eager pass (time given), or the one after
+        the loop."""
+        if not exists(time):
+            return ops.inpaint_blend(vid, inp["known"], inp["mask"], None, None, noise_scheduler,
+                                     normalize=inp["normalize"], final=True)
+        full = lambda v: torch.full((vid.shape[0],), v, device=vid.device, dtype=torch.long)
+        return ops.inpaint_blend(vid, inp["known"], inp["mask"], torch.randn_like(vid), full(time),
+                                 noise_scheduler, times_from=full(time_from) if exists(time_from) else None,
+                                 normalize=inp["normalize"])
+
     @torch.no_grad()
     def p_sample_loop_ddpm(self, unet, shape, video_embed, noise_scheduler, predict_x_start=False,
                            predict_v=False, learned_variance=False, clip_denoised=True,
                            lowres_cond_vid=None, text_encodings=None, cond_scale=1,
-                           is_latent_diffusion=False, lowres_noise_level=None):
+                           is_latent_diffusion=False, lowres_noise_level=None, inpaint_video=None,
+                           inpaint_mask=None, inpaint_resample_times=5):
         """dalle2_video.py:1667-1755.  On the GPU every denoise step after the
         first two is a replay of one captured HIP graph (_DenoiseStepGraph):
         the Unet3D forward(s), the device-side noise draw and the in-place
-        posterior update, with no host launches in between."""
+        posterior update, with no host launches in between.
+
+        inpaint_video / inpaint_mask (at the loop's resolution: `shape`, and
+        (b, f, h, w)) hold the masked part of the clip fixed, as RePaint does
+        (:1719-1751, commented out in the reference): every timestep runs
+        inpaint_resample_times passes, each starting with one
+        ops.inpaint_blend, and a last blend follows the loop."""
         b = shape[0]
+        inp, resample_times = self._inpaint_loop_inputs(unet, shape, inpaint_video, inpaint_mask,
+                                                        inpaint_resample_times, is_latent_diffusion)
         vid = torch.randn(shape, device=self.device)
         if not is_latent_diffusion:
             lowres_cond_vid = maybe(self.normalize_video)(lowres_cond_vid)
+        passes = inpaint_passes([(t, t - 1) for t in reversed(range(0, noise_scheduler.num_timesteps))],
+                                resample_times)
         if self._step_graphs(unet, vid):
             with ops.private_pack_cache():
                 step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
                                          lowres_cond_vid, clip_denoised,
                                          objective=ops.objective_name(predict_x_start, predict_v),
-                                         dyn_percentile=self._dyn_percentile())
-                for time in reversed(range(0, noise_scheduler.num_timesteps)):
-                    step(time)
+                                         dyn_percentile=self._dyn_percentile(),
+                                         **self._inpaint_step_kwargs(inp))
+                for time, _, time_from in passes:
+                    step(time, time_from=time_from)
                 del step
+                if exists(inp):
+                    self._inpaint_blend(vid, inp, noise_scheduler)
             return self.unnormalize_video(vid)
         # the eager loop packs its (unchanging) weights into a private cache too, so
         # sampling never adds entries the trainer's per-update refresh would repack
         x_start = None  # the previous step's x0: the next step's self-conditioning (:1727)
         with (ops.private_pack_cache() if vid.is_cuda else nullcontext()):
-            for time in reversed(range(0, noise_scheduler.num_timesteps)):
+            for time, _, time_from in passes:
                 times = torch.full((b,), time, device=self.device, dtype=torch.long)
+                if exists(inp):
+                    self._inpaint_blend(vid, inp, noise_scheduler, time, time_from)
                 vid, x_start = self.p_sample(unet, vid, times, video_embed=video_embed,
                                              cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
                                              self_cond=x_start,
                                              predict_x_start=predict_x_start, predict_v=predict_v,
                                              noise_scheduler=noise_scheduler, clip_denoised=clip_denoised)
+            if exists(inp):
+                self._inpaint_blend(vid, inp, noise_scheduler)
         return self.unnormalize_video(vid)
 
     @torch.no_grad()
@@ -1508,7 +1665,8 @@ class VideoDecoder(nn.Module):
                            predict_x_start=False, predict_v=False, learned_variance=False,
                            clip_denoised=True, lowres_cond_vid=None, text_encodings=None,
                            cond_scale=1, is_latent_diffusion=False, lowres_noise_level=None,
-                           init_noise=None):
+                           init_noise=None, inpaint_video=None, inpaint_mask=None,
+                           inpaint_resample_times=5):
         """dalle2_video.py:1758-1889 with the keyword names Unet3D has (SURVEY
         Q2: the reference passes image_embed= / lowres_cond_img= and raises):
         one Unet3D forward and one ops.ddim_step per pair of ddim_time_pairs.
@@ -1517,10 +1675,14 @@ class VideoDecoder(nn.Module):
         the draw dead, and there is no reference RNG stream to match (its loop
         never ran).  init_noise (optional) is the start tensor instead of a
         fresh draw.  On the GPU the steps after the first two replay one
-        captured HIP graph, as in p_sample_loop_ddpm."""
+        captured HIP graph, as in p_sample_loop_ddpm.  inpaint_video /
+        inpaint_mask / inpaint_resample_times as in p_sample_loop_ddpm
+        (:1822-1828, 1878-1886): every time pair runs that many passes."""
         assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
         b, eta = shape[0], self.ddim_sampling_eta
-        pairs = ddim_time_pairs(noise_scheduler.num_timesteps, timesteps)
+        inp, resample_times = self._inpaint_loop_inputs(unet, shape, inpaint_video, inpaint_mask,
+                                                        inpaint_resample_times, is_latent_diffusion)
+        passes = inpaint_passes(ddim_time_pairs(noise_scheduler.num_timesteps, timesteps), resample_times)
         if exists(init_noise):
             assert tuple(init_noise.shape) == tuple(shape)
             vid = init_noise.to(device=self.device, dtype=torch.float32).clone()
@@ -1533,21 +1695,28 @@ class VideoDecoder(nn.Module):
                 step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
                                          lowres_cond_vid, clip_denoised, ddim_eta=eta,
                                          objective=ops.objective_name(predict_x_start, predict_v),
-                                         dyn_percentile=self._dyn_percentile())
-                for time, time_next in pairs:
-                    step(time, time_next)
+                                         dyn_percentile=self._dyn_percentile(),
+                                         **self._inpaint_step_kwargs(inp))
+                for time, time_next, time_from in passes:
+                    step(time, time_next, time_from=time_from)
                 del step
+                if exists(inp):
+                    self._inpaint_blend(vid, inp, noise_scheduler)
             return self.unnormalize_video(vid)
         x_start = None  # the previous step's x0: the next step's self-conditioning (:1830)
         with (ops.private_pack_cache() if vid.is_cuda else nullcontext()):
-            for time, time_next in pairs:
+            for time, time_next, time_from in passes:
                 times = torch.full((b,), time, device=self.device, dtype=torch.long)
                 times_next = torch.full((b,), time_next, device=self.device, dtype=torch.long)
+                if exists(inp):
+                    self._inpaint_blend(vid, inp, noise_scheduler, time, time_from)
                 vid, x_start = self.p_sample_ddim(unet, vid, times, times_next, video_embed=video_embed,
                                                   noise_scheduler=noise_scheduler, eta=eta,
                                                   cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
                                                   clip_denoised=clip_denoised, self_cond=x_start,
                                                   predict_x_start=predict_x_start, predict_v=predict_v)
+            if exists(inp):
+                self._inpaint_blend(vid, inp, noise_scheduler)
         return self.unnormalize_video(vid)
 
     @torch.no_grad()
@@ -1563,12 +1732,20 @@ class VideoDecoder(nn.Module):
     @torch.no_grad()
     def sample(self, video=None, video_embed=None, text=None, text_encodings=None, batch_size=1,
                cond_scale=1.0, start_at_unet_number=1, stop_at_unet_number=None,
-               distributed=False, one_unet_in_gpu_at_time=True, cuda="cuda"):
+               distributed=False, one_unet_in_gpu_at_time=True, cuda="cuda", inpaint_video=None,
+               inpaint_mask=None, inpaint_resample_times=5):
+        """inpaint_video (b, c, f, h, w, in the input range) with inpaint_mask
+        (bool, (b, f, h, w) or (b, h, w); True: known) holds the marked part of
+        the clip fixed and generates the rest (RePaint); every unet of the
+        cascade gets the pair resized (nearest) to its frame size."""
         assert self.unconditional or exists(video_embed), \
             "image embed must be present on sampling from decoder unless if trained unconditionally"
         if not self.unconditional:
             batch_size = video_embed.shape[0]
         assert not exists(text_encodings) and not exists(text)
+        inpaint = self._prepare_inpaint(
+            inpaint_video, inpaint_mask, inpaint_resample_times, batch_size,
+            range(start_at_unet_number, default(stop_at_unet_number, self.num_unets) + 1))
         was_training = self.training
         self.eval()
         vid = None
@@ -1593,13 +1770,19 @@ class VideoDecoder(nn.Module):
                 if unet.lowres_cond:
                     lowres_cond_vid = resize_video_to(vid, frame_size,
                                                       clamp_range=self.input_video_range)
+                inpaint_kwargs = {}
+                if exists(inpaint):
+                    inpaint_kwargs = dict(
+                        inpaint_video=resize_video_to(inpaint[0].to(self.device), frame_size),
+                        inpaint_mask=resize_mask_nearest(inpaint[1].to(self.device), frame_size),
+                        inpaint_resample_times=inpaint_resample_times)
                 vid = self.p_sample_loop(unet, shape, video_embed=video_embed,
                                          cond_scale=unet_cond_scale,
                                          lowres_cond_vid=lowres_cond_vid,
                                          predict_x_start=predict_x_start, predict_v=predict_v,
                                          noise_scheduler=noise_scheduler,
                                          timesteps=sample_timesteps,
-                                         clip_denoised=True)
+                                         clip_denoised=True, **inpaint_kwargs)
             if exists(stop_at_unet_number) and stop_at_unet_number == unet_number:
                 break
         self.train(was_training)

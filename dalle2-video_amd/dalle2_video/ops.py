@@ -2804,6 +2804,43 @@ def ddim_step(x, eps, noise, times, times_next, sched, eta, clip_denoised=True, 
     return out, x0
 
 
+def inpaint_blend(x, known, mask, noise, times, sched, times_from=None, normalize=False, final=False):
+    """The RePaint bookkeeping of one sampling pass, in place on the NCTHW f32
+    loop state x (p_sample_loop_ddim, dalle2_video.py:1822-1828, 1878-1886):
+    where the uint8 mask (b, f, h, w) is nonzero x becomes q_sample(known, times)
+    drawn with `noise` (final=True: the known clip itself; noise and times may
+    be None); elsewhere x stays, or with times_from is renoised times_from ->
+    times (NoiseScheduler.q_sample_from_to) with the same `noise`.  normalize:
+    known is in [0, 1] and enters as 2 known - 1.  Returns x."""
+    require_gpu(x, known, mask, noise, times, times_from)
+    if x.dim() != 5 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.DVError("inpaint_blend: x must be a contiguous NCTHW f32 tensor (it is updated in place)")
+    B, C, T, H, W = x.shape
+    if known.shape != x.shape or known.dtype != torch.float32 or not known.is_contiguous():
+        raise _lib.DVError(f"inpaint_blend: known must be a contiguous f32 tensor shaped like x {tuple(x.shape)}")
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, T, H, W) or not mask.is_contiguous():
+        raise _lib.DVError(f"inpaint_blend: mask must be a contiguous uint8 tensor of shape {(B, T, H, W)}")
+    if final:
+        if times_from is not None:
+            raise _lib.DVError("inpaint_blend: the final blend takes no times_from")
+        noise = times = None
+    else:
+        if noise is None or times is None:
+            raise _lib.DVError("inpaint_blend: noise and times may be None only with final=True")
+        if noise.shape != x.shape or noise.dtype != torch.float32 or not noise.is_contiguous():
+            raise _lib.DVError("inpaint_blend: noise must be a contiguous f32 tensor shaped like x")
+        for name, tt in (("times", times), ("times_from", times_from)):
+            if tt is not None and (tt.dtype != torch.int64 or tt.numel() != B or not tt.is_contiguous()):
+                raise _lib.DVError(f"inpaint_blend: {name} holds one contiguous int64 entry per sample")
+    n = x.numel()
+    nbytes = (8 if final else 12) * n + mask.numel() + 4 * n  # reads (x, known[, noise]), mask, the store
+    _launch("inpaint_blend_kernel", 0.0, nbytes,
+            lambda: call("dv_inpaint_blend", ptr(x), ptr(known), ptr(mask), ptr(noise), ptr(times), ptr(times_from),
+                         ptr(sched.sqrt_alphas_cumprod), ptr(sched.sqrt_one_minus_alphas_cumprod), B, C, T, H, W,
+                         int(bool(normalize)), int(bool(final)), sched.sqrt_alphas_cumprod.numel(), stream()))
+    return x
+
+
 def resize_nearest(video, size, clamp_range=None):
     """Per-frame nearest resize of an NCTHW clip to size x size."""
     require_gpu(video)

@@ -519,6 +519,30 @@ int dv_q_sample_sc(int dtype, const float* x0, const float* noise, const long lo
                    int sc_dtype, void* y, int B, int C, int Csc, int T, int H, int W, int cpad,
                    int normalize, int num_timesteps, void* stream);
 
+/* ---- inpainting (ABI 9) ----------------------------------------------------
+ * The per-pass RePaint bookkeeping (arXiv 2201.09865; the DDIM loop at
+ * dalle2_video.py:1822-1828, 1878-1886) on the NCTHW f32 loop state x, in
+ * place, in one launch.  mask is [B][T][H][W] bytes shared by all C channels
+ * (nonzero: keep the known clip here); k = 2 known - 1 when normalize != 0,
+ * else known; a = sqrt_ac, s = sqrt_1m_ac.  Per element:
+ *   masked,   final != 0      : x = k
+ *   masked,   final == 0      : x = a[t] k + s[t] noise       (q_sample at t)
+ *   unmasked, t_from == NULL  : x is left as it is
+ *   unmasked, t_from != NULL  : x = x a[t]/a[u] + noise (s[t] a[u] - s[u] a[t])/a[u],
+ *                               u = t_from[b] < t[b]
+ *                               (NoiseScheduler.q_sample_from_to u -> t)
+ * Both noised branches read the same `noise` tensor (shaped like x): every
+ * element belongs to one of them.  With final != 0, noise, t and the tables
+ * may be NULL and t_from must be.  A sample with t outside
+ * [0, num_timesteps), or with t_from given and t_from < 0 or t_from >= t, has
+ * every element this call writes set to NaN; no table is read out of bounds.
+ * 16-byte accesses when H*W % 4 == 0 and the pointers are aligned (mask: 4
+ * bytes), one element per thread otherwise.  No atomics, no workspace.       */
+int dv_inpaint_blend(float* x, const float* known, const unsigned char* mask, const float* noise,
+                     const long long* t, const long long* t_from, const float* sqrt_ac,
+                     const float* sqrt_1m_ac, int B, int C, int T, int H, int W, int normalize,
+                     int final, int num_timesteps, void* stream);
+
 /* ---- time conditioning MLPs (Unet3D.to_time_hiddens / to_time_tokens /
  * to_time_cond, dalle2_video.py:348-357; ResnetBlock3D.time_mlp, :152-155)
  * SinusoidalPosEmb (:349): out[b] = [sin(t*f), cos(t*f)], freqs = dim/2
