@@ -1046,8 +1046,8 @@ class _DenoiseStepGraph:
     For a unet built with cond_on_video_embeds=True, `video_embed` is a third
     fixed device buffer read by every forward of the step.
 
-    A unet built with self_cond=True has no captured step: its loops run
-    eagerly (VideoDecoder._step_graphs) and this class refuses it.
+    A unet built with self_cond=True has no captured step: its loop runs
+    _EagerDenoiseStep (VideoDecoder._step_graphs) and this class refuses it.
 
     Inpainting (inpaint_known / inpaint_mask, keyword-only: the known clip at
     the loop's resolution in the input range, and its uint8 mask) puts a noise
@@ -1093,16 +1093,16 @@ class _DenoiseStepGraph:
         return ops.dynamic_threshold_scale(self.x, pred, self.t, self.sched, self.objective,
                                            self.dyn_percentile, ddim=ddim, out=self.dyn_s)
 
-    def _ddpm_update(self, eps):
-        noise = torch.randn_like(self.x)
-        ops.p_sample_step(self.x, eps, noise, self.t, self.sched, self.clip, out=self.x, want_x0=False,
-                          objective=self.objective, dyn_scale=self._dyn_scale(eps, False))
-
-    def _ddim_update(self, eps):
-        noise = torch.randn_like(self.x) if self.ddim_eta != 0 else None
-        ops.ddim_step(self.x, eps, noise, self.t, self.t_next, self.sched, self.ddim_eta, self.clip,
-                      out=self.x, want_x0=False, objective=self.objective,
-                      dyn_scale=self._dyn_scale(eps, True))
+    def _update(self, pred):
+        """The sampler's update rule, written back into x: the noise draw, the
+        quantile launch (if any), then the step kernel."""
+        ddim = exists(self.ddim_eta)
+        noise = torch.randn_like(self.x) if not ddim or self.ddim_eta != 0 else None
+        kw = dict(out=self.x, want_x0=False, objective=self.objective, dyn_scale=self._dyn_scale(pred, ddim))
+        if ddim:
+            ops.ddim_step(self.x, pred, noise, self.t, self.t_next, self.sched, self.ddim_eta, self.clip, **kw)
+        else:
+            ops.p_sample_step(self.x, pred, noise, self.t, self.sched, self.clip, **kw)
 
     def _body(self, renoise=False):
         x, unet = self.x, self.unet
@@ -1121,8 +1121,7 @@ class _DenoiseStepGraph:
             eps = unet.forward_with_cond_scale(x, self.t, video_embed=self.video_embed,
                                                cond_scale=self.cond_scale,
                                                lowres_cond_video=self.lowres)
-        # (no bound method kept on self: `del step` must free the graph at once)
-        (self._ddim_update if exists(self.ddim_eta) else self._ddpm_update)(eps)
+        self._update(eps)
 
     def __call__(self, time, time_next=None, time_from=None):
         self.t.fill_(time)
@@ -1145,6 +1144,33 @@ class _DenoiseStepGraph:
                 self._body(renoise)
                 ops.gn_graph_boundary(self.x.device)
         getattr(self, slot).replay()
+
+
+class _EagerDenoiseStep:
+    """The call of _DenoiseStepGraph with every launch issued every time: the
+    pass's blend (with inpainting inputs), then the step p_sample /
+    p_sample_ddim run (VideoDecoder._p_sample, the NCTHW route through
+    forward_with_cond_scale).  That step is out of place, so the call rebinds
+    the loop state `x`; the x0 it returns is the self-conditioning input of
+    the next step (:1727, :1830)."""
+
+    def __init__(self, decoder, unet, x, video_embed, noise_scheduler, cond_scale, lowres_cond_vid,
+                 clip_denoised, ddim_eta=None, predict_x_start=False, predict_v=False, **inpaint):
+        self.decoder, self.x, self.x_start = decoder, x, None
+        self.sched, self.ddim_eta, self.inpaint = noise_scheduler, ddim_eta, inpaint
+        self.step = partial(decoder._p_sample, unet, ddim_eta=ddim_eta, video_embed=video_embed,
+                            noise_scheduler=noise_scheduler, cond_scale=cond_scale,
+                            lowres_cond_vid=lowres_cond_vid, clip_denoised=clip_denoised,
+                            predict_x_start=predict_x_start, predict_v=predict_v)
+
+    def __call__(self, time, time_next=None, time_from=None):
+        x = self.x
+        full = lambda v: torch.full((x.shape[0],), v, device=x.device, dtype=torch.long)
+        times = full(time)
+        times_next = full(time_next) if exists(self.ddim_eta) else None
+        if self.inpaint:
+            self.decoder._inpaint_blend(x, self.sched, time, time_from, **self.inpaint)
+        self.x, self.x_start = self.step(x, times, times_next, self_cond=self.x_start)
 
 
 # ---------------------------------------------------------------------------
@@ -1472,17 +1498,31 @@ class VideoDecoder(nn.Module):
                  cond_scale=1.0, lowres_cond_vid=None, self_cond=None, predict_x_start=False,
                  predict_v=False, learned_variance=False, clip_denoised=True,
                  lowres_noise_level=None, noise=None):
+        return self._p_sample(unet, x, t, None, ddim_eta=None, video_embed=video_embed,
+                              noise_scheduler=noise_scheduler, cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
+                              clip_denoised=clip_denoised, noise=noise, predict_x_start=predict_x_start,
+                              predict_v=predict_v, self_cond=self_cond)
+
+    def _p_sample(self, unet, x, t, t_next, *, ddim_eta, video_embed, noise_scheduler, cond_scale, lowres_cond_vid,
+                  clip_denoised, predict_x_start, predict_v, self_cond, noise=None):
+        """The eager step of both samplers, (x_next, x0): one forward, the
+        noise draw, the quantile launch (with dynamic thresholding) and the
+        update rule: ops.p_sample_step for ddim_eta None, else ops.ddim_step
+        t -> t_next, which draws nothing at eta == 0."""
         assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
         pred = unet.forward_with_cond_scale(x, t, video_embed=video_embed,
                                             cond_scale=cond_scale,
                                             lowres_cond_video=lowres_cond_vid,
                                             **self._self_cond_kwargs(unet, self_cond))
-        noise = default(noise, lambda: torch.randn_like(x))
+        ddim = exists(ddim_eta)
+        if not ddim or ddim_eta != 0:
+            noise = default(noise, lambda: torch.randn_like(x))
         objective = ops.objective_name(predict_x_start, predict_v)
-        out, x0 = ops.p_sample_step(x, pred, noise, t, noise_scheduler, clip_denoised, objective=objective,
-                                    dyn_scale=self._dyn_scale(x, pred, t, noise_scheduler, objective,
-                                                              clip_denoised, ddim=False))
-        return out, x0
+        kw = dict(objective=objective, dyn_scale=self._dyn_scale(x, pred, t, noise_scheduler, objective,
+                                                                 clip_denoised, ddim=ddim))
+        if ddim:
+            return ops.ddim_step(x, pred, noise, t, t_next, noise_scheduler, ddim_eta, clip_denoised, **kw)
+        return ops.p_sample_step(x, pred, noise, t, noise_scheduler, clip_denoised, **kw)
 
     @staticmethod
     def _self_cond_kwargs(unet, self_cond):
@@ -1504,9 +1544,6 @@ class VideoDecoder(nn.Module):
         unet: its step (x0 handed from one step to the next) is not captured,
         the loop launches every step."""
         return vid.is_cuda and self.sample_graphs and not getattr(unet, "self_cond", False)
-
-    def _dyn_percentile(self):
-        return self.dynamic_thres_percentile if self.use_dynamic_thres else None
 
     # ---- inpainting (RePaint, arXiv 2201.09865; dalle2_video.py:1775-1886) ----
     @staticmethod
@@ -1556,10 +1593,11 @@ class VideoDecoder(nn.Module):
 
     def _inpaint_loop_inputs(self, unet, shape, inpaint_video, inpaint_mask, inpaint_resample_times,
                              is_latent_diffusion):
-        """(keyword inputs of the blend, resample_times) of one loop; the pair
-        comes at the loop's resolution.  (None, 1) without inpainting."""
+        """(inpainting keyword inputs of the step objects and of _inpaint_blend,
+        resample_times) of one loop; the pair comes at the loop's resolution.
+        ({}, 1) without inpainting."""
         if not self._inpaint_requested(inpaint_video, inpaint_mask, inpaint_resample_times, [unet]):
-            return None, 1
+            return {}, 1
         b, _, f, h, w = shape
         if tuple(inpaint_video.shape) != tuple(shape) or tuple(inpaint_mask.shape) != (b, f, h, w):
             raise ValueError(f"the loop samples {tuple(shape)}: inpaint_video {tuple(inpaint_video.shape)} and "
@@ -1567,24 +1605,21 @@ class VideoDecoder(nn.Module):
         known = inpaint_video.to(device=self.device, dtype=torch.float32).contiguous()
         mask = inpaint_mask.to(device=self.device).ne(0).to(torch.uint8).contiguous()
         # normalize_video, like training data, folded into the blend kernel
-        return dict(known=known, mask=mask,
-                    normalize=self.auto_normalize_video and not is_latent_diffusion), int(inpaint_resample_times)
+        return dict(inpaint_known=known, inpaint_mask=mask,
+                    inpaint_normalize=self.auto_normalize_video and not is_latent_diffusion), \
+            int(inpaint_resample_times)
 
-    @staticmethod
-    def _inpaint_step_kwargs(inp):
-        return dict(inpaint_known=inp["known"], inpaint_mask=inp["mask"],
-                    inpaint_normalize=inp["normalize"]) if exists(inp) else {}
-
-    def _inpaint_blend(self, vid, inp, noise_scheduler, time=None, time_from=None):
+    def _inpaint_blend(self, vid, noise_scheduler, time=None, time_from=None, *, inpaint_known, inpaint_mask,
+                       inpaint_normalize):
         """The blend in front of one eager pass (time given), or the one after
         the loop."""
         if not exists(time):
-            return ops.inpaint_blend(vid, inp["known"], inp["mask"], None, None, noise_scheduler,
-                                     normalize=inp["normalize"], final=True)
+            return ops.inpaint_blend(vid, inpaint_known, inpaint_mask, None, None, noise_scheduler,
+                                     normalize=inpaint_normalize, final=True)
         full = lambda v: torch.full((vid.shape[0],), v, device=vid.device, dtype=torch.long)
-        return ops.inpaint_blend(vid, inp["known"], inp["mask"], torch.randn_like(vid), full(time),
+        return ops.inpaint_blend(vid, inpaint_known, inpaint_mask, torch.randn_like(vid), full(time),
                                  noise_scheduler, times_from=full(time_from) if exists(time_from) else None,
-                                 normalize=inp["normalize"])
+                                 normalize=inpaint_normalize)
 
     @torch.no_grad()
     def p_sample_loop_ddpm(self, unet, shape, video_embed, noise_scheduler, predict_x_start=False,
@@ -1602,42 +1637,45 @@ class VideoDecoder(nn.Module):
         (:1719-1751, commented out in the reference): every timestep runs
         inpaint_resample_times passes, each starting with one
         ops.inpaint_blend, and a last blend follows the loop."""
-        b = shape[0]
+        return self._sample_loop(
+            unet, shape, [(t, t - 1) for t in reversed(range(noise_scheduler.num_timesteps))], video_embed,
+            noise_scheduler, ddim_eta=None, predict_x_start=predict_x_start, predict_v=predict_v,
+            clip_denoised=clip_denoised, lowres_cond_vid=lowres_cond_vid, cond_scale=cond_scale,
+            is_latent_diffusion=is_latent_diffusion, inpaint_video=inpaint_video, inpaint_mask=inpaint_mask,
+            inpaint_resample_times=inpaint_resample_times)
+
+    def _sample_loop(self, unet, shape, pairs, video_embed, noise_scheduler, *, ddim_eta, predict_x_start, predict_v,
+                     clip_denoised, lowres_cond_vid, cond_scale, is_latent_diffusion, inpaint_video, inpaint_mask,
+                     inpaint_resample_times, init_noise=None):
+        """The loop of every sampler over its (time, time_next) `pairs`, newest
+        first: ddim_eta None is DDPM, a float the DDIM update.  One step object
+        runs every pass: the captured _DenoiseStepGraph, or _EagerDenoiseStep
+        (_step_graphs says which)."""
         inp, resample_times = self._inpaint_loop_inputs(unet, shape, inpaint_video, inpaint_mask,
                                                         inpaint_resample_times, is_latent_diffusion)
-        vid = torch.randn(shape, device=self.device)
+        passes = inpaint_passes(pairs, resample_times)
+        if exists(init_noise):
+            assert tuple(init_noise.shape) == tuple(shape)
+            vid = init_noise.to(device=self.device, dtype=torch.float32).clone()
+        else:
+            vid = torch.randn(shape, device=self.device)
         if not is_latent_diffusion:
             lowres_cond_vid = maybe(self.normalize_video)(lowres_cond_vid)
-        passes = inpaint_passes([(t, t - 1) for t in reversed(range(0, noise_scheduler.num_timesteps))],
-                                resample_times)
-        if self._step_graphs(unet, vid):
-            with ops.private_pack_cache():
-                step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
-                                         lowres_cond_vid, clip_denoised,
-                                         objective=ops.objective_name(predict_x_start, predict_v),
-                                         dyn_percentile=self._dyn_percentile(),
-                                         **self._inpaint_step_kwargs(inp))
-                for time, _, time_from in passes:
-                    step(time, time_from=time_from)
-                del step
-                if exists(inp):
-                    self._inpaint_blend(vid, inp, noise_scheduler)
-            return self.unnormalize_video(vid)
+        common = (self, unet, vid, video_embed, noise_scheduler, cond_scale, lowres_cond_vid, clip_denoised, ddim_eta)
         # the eager loop packs its (unchanging) weights into a private cache too, so
         # sampling never adds entries the trainer's per-update refresh would repack
-        x_start = None  # the previous step's x0: the next step's self-conditioning (:1727)
         with (ops.private_pack_cache() if vid.is_cuda else nullcontext()):
-            for time, _, time_from in passes:
-                times = torch.full((b,), time, device=self.device, dtype=torch.long)
-                if exists(inp):
-                    self._inpaint_blend(vid, inp, noise_scheduler, time, time_from)
-                vid, x_start = self.p_sample(unet, vid, times, video_embed=video_embed,
-                                             cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
-                                             self_cond=x_start,
-                                             predict_x_start=predict_x_start, predict_v=predict_v,
-                                             noise_scheduler=noise_scheduler, clip_denoised=clip_denoised)
-            if exists(inp):
-                self._inpaint_blend(vid, inp, noise_scheduler)
+            if self._step_graphs(unet, vid):
+                step = _DenoiseStepGraph(*common, ops.objective_name(predict_x_start, predict_v),
+                                         self.dynamic_thres_percentile if self.use_dynamic_thres else None, **inp)
+            else:
+                step = _EagerDenoiseStep(*common, predict_x_start, predict_v, **inp)
+            for time, time_next, time_from in passes:
+                step(time, time_next, time_from)
+            vid = step.x  # the eager step rebinds it; the captured one updates it in place
+            del step  # frees the captured graphs at once
+            if inp:
+                self._inpaint_blend(vid, noise_scheduler, **inp)
         return self.unnormalize_video(vid)
 
     @torch.no_grad()
@@ -1647,18 +1685,10 @@ class VideoDecoder(nn.Module):
         """One DDIM step t -> t_next (the body of the loop at
         dalle2_video.py:1811-1876): returns (x_next, x0).  At eta == 0 no noise
         is drawn."""
-        assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
-        pred = unet.forward_with_cond_scale(x, t, video_embed=video_embed,
-                                            cond_scale=cond_scale,
-                                            lowres_cond_video=lowres_cond_vid,
-                                            **self._self_cond_kwargs(unet, self_cond))
-        if eta != 0:
-            noise = default(noise, lambda: torch.randn_like(x))
-        objective = ops.objective_name(predict_x_start, predict_v)
-        return ops.ddim_step(x, pred, noise, t, t_next, noise_scheduler, eta, clip_denoised,
-                             objective=objective,
-                             dyn_scale=self._dyn_scale(x, pred, t, noise_scheduler, objective,
-                                                       clip_denoised, ddim=True))
+        return self._p_sample(unet, x, t, t_next, ddim_eta=float(eta), video_embed=video_embed,
+                              noise_scheduler=noise_scheduler, cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
+                              clip_denoised=clip_denoised, noise=noise, predict_x_start=predict_x_start,
+                              predict_v=predict_v, self_cond=self_cond)
 
     @torch.no_grad()
     def p_sample_loop_ddim(self, unet, shape, video_embed, noise_scheduler, timesteps, eta=1.0,
@@ -1679,45 +1709,12 @@ class VideoDecoder(nn.Module):
         inpaint_mask / inpaint_resample_times as in p_sample_loop_ddpm
         (:1822-1828, 1878-1886): every time pair runs that many passes."""
         assert not (cond_scale != 1.0 and not self.can_classifier_guidance)
-        b, eta = shape[0], self.ddim_sampling_eta
-        inp, resample_times = self._inpaint_loop_inputs(unet, shape, inpaint_video, inpaint_mask,
-                                                        inpaint_resample_times, is_latent_diffusion)
-        passes = inpaint_passes(ddim_time_pairs(noise_scheduler.num_timesteps, timesteps), resample_times)
-        if exists(init_noise):
-            assert tuple(init_noise.shape) == tuple(shape)
-            vid = init_noise.to(device=self.device, dtype=torch.float32).clone()
-        else:
-            vid = torch.randn(shape, device=self.device)
-        if not is_latent_diffusion:
-            lowres_cond_vid = maybe(self.normalize_video)(lowres_cond_vid)
-        if self._step_graphs(unet, vid):
-            with ops.private_pack_cache():
-                step = _DenoiseStepGraph(self, unet, vid, video_embed, noise_scheduler, cond_scale,
-                                         lowres_cond_vid, clip_denoised, ddim_eta=eta,
-                                         objective=ops.objective_name(predict_x_start, predict_v),
-                                         dyn_percentile=self._dyn_percentile(),
-                                         **self._inpaint_step_kwargs(inp))
-                for time, time_next, time_from in passes:
-                    step(time, time_next, time_from=time_from)
-                del step
-                if exists(inp):
-                    self._inpaint_blend(vid, inp, noise_scheduler)
-            return self.unnormalize_video(vid)
-        x_start = None  # the previous step's x0: the next step's self-conditioning (:1830)
-        with (ops.private_pack_cache() if vid.is_cuda else nullcontext()):
-            for time, time_next, time_from in passes:
-                times = torch.full((b,), time, device=self.device, dtype=torch.long)
-                times_next = torch.full((b,), time_next, device=self.device, dtype=torch.long)
-                if exists(inp):
-                    self._inpaint_blend(vid, inp, noise_scheduler, time, time_from)
-                vid, x_start = self.p_sample_ddim(unet, vid, times, times_next, video_embed=video_embed,
-                                                  noise_scheduler=noise_scheduler, eta=eta,
-                                                  cond_scale=cond_scale, lowres_cond_vid=lowres_cond_vid,
-                                                  clip_denoised=clip_denoised, self_cond=x_start,
-                                                  predict_x_start=predict_x_start, predict_v=predict_v)
-            if exists(inp):
-                self._inpaint_blend(vid, inp, noise_scheduler)
-        return self.unnormalize_video(vid)
+        return self._sample_loop(
+            unet, shape, ddim_time_pairs(noise_scheduler.num_timesteps, timesteps), video_embed, noise_scheduler,
+            ddim_eta=self.ddim_sampling_eta, init_noise=init_noise, predict_x_start=predict_x_start,
+            predict_v=predict_v, clip_denoised=clip_denoised, lowres_cond_vid=lowres_cond_vid,
+            cond_scale=cond_scale, is_latent_diffusion=is_latent_diffusion, inpaint_video=inpaint_video,
+            inpaint_mask=inpaint_mask, inpaint_resample_times=inpaint_resample_times)
 
     @torch.no_grad()
     def p_sample_loop(self, *args, noise_scheduler, timesteps=None, **kwargs):

@@ -2712,36 +2712,22 @@ def p_sample_step(x, eps, noise, times, sched, clip_denoised=True, out=None, wan
     (:1589-1595).  dyn_scale (dynamic_threshold_scale) replaces the clamp at 1
     by clamp(x0, -s, s)/s."""
     code = _objective_code(objective)
-    if code != _lib.OBJ_EPS or dyn_scale is not None:
-        require_gpu(x, eps, noise, times)
-        xf = x.float().contiguous()
-        nz = noise.float().contiguous()
-        t = times.to(torch.int64).contiguous()
-        B, C, T, H, W = xf.shape
-        ef, ld, edt = _pred_layout("p_sample", eps, xf)
-        _check_dyn_scale("p_sample", dyn_scale, B, clip_denoised)
-        if out is None:
-            out = torch.empty_like(xf)
-        elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != xf.shape:
-            raise _lib.DVError("p_sample: out must be a contiguous f32 tensor shaped like x")
-        x0 = torch.empty_like(xf) if want_x0 else None
-        kx, kp = _x0_tables(sched, objective)
-        call("dv_p_sample_obj", edt, ptr(xf), ptr(ef), ld, ptr(nz), ptr(t), ptr(kx), ptr(kp),
-             ptr(sched.posterior_mean_coef1), ptr(sched.posterior_mean_coef2),
-             ptr(sched.posterior_log_variance_clipped), ptr(dyn_scale), ptr(out), ptr(x0), B, C, T, H, W,
-             int(clip_denoised), code, sched.sqrt_recip_alphas_cumprod.numel(), stream())
-        return out, x0
+    obj_entry = code != _lib.OBJ_EPS or dyn_scale is not None
     require_gpu(x, eps, noise, times)
     xf = x.float().contiguous()
     nz = noise.float().contiguous()
     t = times.to(torch.int64).contiguous()
     B, C, T, H, W = xf.shape
-    if eps.dim() == 5:
-        ef = eps.float().contiguous()
-        ld, edt = 0, _lib.DV_F32
+    if obj_entry:
+        ef, ld, edt = _pred_layout("p_sample", eps, xf)
+        _check_dyn_scale("p_sample", dyn_scale, B, clip_denoised)
+    elif eps.dim() == 5:
+        # dv_p_sample's callers have always had fewer checks than _pred_layout
+        # makes, worded with "eps": an NCTHW eps is taken as it comes, and
+        # channels-last frames are checked after their strides and without (H, W)
+        ef, ld, edt = eps.float().contiguous(), 0, _lib.DV_F32
     else:
-        ef = eps
-        ld, edt = cl_ld(eps), dt(eps)
+        ef, ld, edt = eps, cl_ld(eps), dt(eps)
         if eps.shape[0] != B * T or eps.shape[-1] < C:
             raise _lib.DVError(f"p_sample: eps {tuple(eps.shape)} does not match x {tuple(xf.shape)}")
     if out is None:
@@ -2749,6 +2735,13 @@ def p_sample_step(x, eps, noise, times, sched, clip_denoised=True, out=None, wan
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != xf.shape:
         raise _lib.DVError("p_sample: out must be a contiguous f32 tensor shaped like x")
     x0 = torch.empty_like(xf) if want_x0 else None
+    if obj_entry:
+        kx, kp = _x0_tables(sched, objective)
+        call("dv_p_sample_obj", edt, ptr(xf), ptr(ef), ld, ptr(nz), ptr(t), ptr(kx), ptr(kp),
+             ptr(sched.posterior_mean_coef1), ptr(sched.posterior_mean_coef2),
+             ptr(sched.posterior_log_variance_clipped), ptr(dyn_scale), ptr(out), ptr(x0), B, C, T, H, W,
+             int(clip_denoised), code, sched.sqrt_recip_alphas_cumprod.numel(), stream())
+        return out, x0
     call("dv_p_sample", edt, ptr(xf), ptr(ef), ld, ptr(nz), ptr(t), ptr(sched.sqrt_recip_alphas_cumprod),
          ptr(sched.sqrt_recipm1_alphas_cumprod), ptr(sched.posterior_mean_coef1),
          ptr(sched.posterior_mean_coef2), ptr(sched.posterior_log_variance_clipped), ptr(out), ptr(x0),

@@ -211,6 +211,56 @@ def test_step_graph_inpaint_inputs_are_keyword_only():
         assert params[n].kind is inspect.Parameter.KEYWORD_ONLY
 
 
+_REQ = "required"
+_SAMPLING_SIGNATURES = {  # the callers' contract: parameter names, order and defaults
+    "p_sample": [
+        ("self", _REQ), ("unet", _REQ), ("x", _REQ), ("t", _REQ), ("video_embed", _REQ), ("noise_scheduler", _REQ),
+        ("text_encodings", None), ("cond_scale", 1.0), ("lowres_cond_vid", None), ("self_cond", None),
+        ("predict_x_start", False), ("predict_v", False), ("learned_variance", False), ("clip_denoised", True),
+        ("lowres_noise_level", None), ("noise", None)],
+    "p_sample_ddim": [
+        ("self", _REQ), ("unet", _REQ), ("x", _REQ), ("t", _REQ), ("t_next", _REQ), ("video_embed", _REQ),
+        ("noise_scheduler", _REQ), ("eta", _REQ), ("cond_scale", 1.0), ("lowres_cond_vid", None),
+        ("clip_denoised", True), ("noise", None), ("predict_x_start", False), ("predict_v", False),
+        ("self_cond", None)],
+    "p_sample_loop_ddpm": [
+        ("self", _REQ), ("unet", _REQ), ("shape", _REQ), ("video_embed", _REQ), ("noise_scheduler", _REQ),
+        ("predict_x_start", False), ("predict_v", False), ("learned_variance", False), ("clip_denoised", True),
+        ("lowres_cond_vid", None), ("text_encodings", None), ("cond_scale", 1), ("is_latent_diffusion", False),
+        ("lowres_noise_level", None), ("inpaint_video", None), ("inpaint_mask", None),
+        ("inpaint_resample_times", 5)],
+    "p_sample_loop_ddim": [
+        ("self", _REQ), ("unet", _REQ), ("shape", _REQ), ("video_embed", _REQ), ("noise_scheduler", _REQ),
+        ("timesteps", _REQ), ("eta", 1.0), ("predict_x_start", False), ("predict_v", False),
+        ("learned_variance", False), ("clip_denoised", True), ("lowres_cond_vid", None), ("text_encodings", None),
+        ("cond_scale", 1), ("is_latent_diffusion", False), ("lowres_noise_level", None), ("init_noise", None),
+        ("inpaint_video", None), ("inpaint_mask", None), ("inpaint_resample_times", 5)],
+    "_DenoiseStepGraph.__init__": [
+        ("self", _REQ), ("decoder", _REQ), ("unet", _REQ), ("x", _REQ), ("video_embed", _REQ),
+        ("noise_scheduler", _REQ), ("cond_scale", _REQ), ("lowres_cond_vid", _REQ), ("clip_denoised", _REQ),
+        ("ddim_eta", None), ("objective", "eps"), ("dyn_percentile", None), ("inpaint_known", None),
+        ("inpaint_mask", None), ("inpaint_normalize", False)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(_SAMPLING_SIGNATURES))
+def test_sampling_entry_points_keep_their_signatures(name):
+    import inspect
+
+    from dalle2_video import dalle2_video as D
+
+    fn = D._DenoiseStepGraph.__init__ if name.startswith("_Denoise") else getattr(D.VideoDecoder, name)
+    params = inspect.signature(fn).parameters.values()
+    got = [(p.name, _REQ if p.default is inspect.Parameter.empty else p.default) for p in params]
+    assert got == _SAMPLING_SIGNATURES[name]
+    # equal defaults of another type (1 == 1.0 == True) are not the same default
+    assert [type(d) for _, d in got] == [type(d) for _, d in _SAMPLING_SIGNATURES[name]]
+    kinds = {p.name: p.kind for p in params}
+    keyword_only = {"inpaint_known", "inpaint_mask", "inpaint_normalize"} if name.startswith("_Denoise") else set()
+    assert {n for n, k in kinds.items() if k is inspect.Parameter.KEYWORD_ONLY} == keyword_only
+    assert all(k is inspect.Parameter.POSITIONAL_OR_KEYWORD for n, k in kinds.items() if n not in keyword_only)
+
+
 def test_abi_is_9_and_declares_the_blend():
     from dalle2_video import _lib
 

@@ -443,6 +443,49 @@ def test_dyn_scale_needs_clip():
         ops.p_sample_step(x.cuda(), pred.cuda(), z.cuda(), t.cuda(), s, objective="x_start")
 
 
+_X = "(3, 3, 2, 8, 8)"  # _mixed_batch's clip: 6 frames of 8 x 8 x 3
+_OUT = "p_sample: out must be a contiguous f32 tensor shaped like x"
+_MALFORMED = {  # case: (objective, the argument that is wrong, the whole message)
+    "eps_out_dtype": ("eps", dict(out=lambda: torch.empty(3, 3, 2, 8, 8, dtype=torch.bfloat16)), _OUT),
+    "eps_out_shape": ("eps", dict(out=lambda: torch.empty(3, 3, 2, 8, 4)), _OUT),
+    "v_out_dtype": ("v", dict(out=lambda: torch.empty(3, 3, 2, 8, 8, dtype=torch.bfloat16)), _OUT),
+    "v_out_shape": ("v", dict(out=lambda: torch.empty(3, 3, 2, 8, 4)), _OUT),
+    # the eps entry names the channels-last prediction "eps", the objective entry "pred"
+    "eps_cl_frames": ("eps", dict(eps=lambda: torch.zeros(5, 8, 8, 3)),
+                      f"p_sample: eps (5, 8, 8, 3) does not match x {_X}"),
+    "eps_cl_channels": ("eps", dict(eps=lambda: torch.zeros(6, 8, 8, 2)),
+                        f"p_sample: eps (6, 8, 8, 2) does not match x {_X}"),
+    "v_cl_frames": ("v", dict(eps=lambda: torch.zeros(5, 8, 8, 3)),
+                    f"p_sample: pred (5, 8, 8, 3) does not match x {_X}"),
+    "v_cl_channels": ("v", dict(eps=lambda: torch.zeros(6, 8, 8, 2)),
+                      f"p_sample: pred (6, 8, 8, 2) does not match x {_X}"),
+    "v_cl_hw": ("v", dict(eps=lambda: torch.zeros(6, 4, 16, 3)),
+                f"p_sample: pred (6, 4, 16, 3) does not match x {_X}"),
+    "v_ncthw_shape": ("v", dict(eps=lambda: torch.zeros(3, 3, 2, 4, 16)),
+                      f"p_sample: pred (3, 3, 2, 4, 16) does not match x {_X}"),
+    "eps_dyn_scale_length": ("eps", dict(dyn_scale=lambda: torch.ones(2)),
+                             "p_sample: dyn_scale holds one contiguous f32 value per sample"),
+    "v_dyn_scale_length": ("v", dict(dyn_scale=lambda: torch.ones(2)),
+                           "p_sample: dyn_scale holds one contiguous f32 value per sample"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(_MALFORMED))
+def test_p_sample_step_rejects_malformed_inputs(case):
+    """Each entry of ops.p_sample_step (dv_p_sample for a plain eps step,
+    dv_p_sample_obj otherwise) refuses a malformed argument before any launch,
+    with the message it has always had."""
+    from dalle2_video import _lib, ops
+
+    objective, wrong, message = _MALFORMED[case]
+    x, pred, z, t, _ = _mixed_batch()
+    kw = dict(eps=pred.cuda(), objective=objective)
+    kw.update({k: make().cuda() for k, make in wrong.items()})
+    with pytest.raises(_lib.DVError) as e:
+        ops.p_sample_step(x.cuda(), kw.pop("eps"), z.cuda(), t.cuda(), _sched("cosine"), **kw)
+    assert str(e.value) == message
+
+
 # ---------------------------------------------------------------------------
 # decoder step vs the oracle Unet3D
 # ---------------------------------------------------------------------------
